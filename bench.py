@@ -3,8 +3,13 @@
 standard-Q quantisation on 8192x8192 grayscale frames (config C3), plus the
 achieved fraction of the MI355X HBM roofline, at 1/2/4/8 GPUs.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N bench.py --gpus N ...   (one process per GPU)
+
+A plain run does only what the headline needs: it sets up the frames, warms
+up, times the K steps, writes the last step's output if --dump-outputs is
+given and prints the JSON line.  Everything under "Also reported" below, the
+parity spot-check and the sustained phase run only with --full.
 
 With --gpus N > 1 and no launcher (WORLD_SIZE unset) the parent process does
 not import torch or touch the GPU: it starts N child processes of this script
@@ -22,7 +27,15 @@ profiles/r02/kbench2_sets_r02.log).  Weak scaling: every rank processes its own 
 frames are independent), no collective in the timed region; value = pixels
 of all ranks / max-over-ranks time.
 
-Also reported (not the headline): the other kernels of the path (fp32 compat
+--dump-outputs DIR writes, after the timed region, the coefficient plane the
+last timed step produced (what a caller of that launch receives) as
+DIR/fwd_coefficients.npy, float32 (rank r > 0: fwd_coefficients_rank<r>.npy).
+A plane above DUMP_BUDGET_BYTES / ranks is written as a fixed, seeded sample of
+its 8-row tile bands (dump_rows), the same rows in every run.  The frames are
+the same from run to run, so two builds run with the same arguments can be
+compared output for output.
+
+Also reported with --full (not the headline): the other kernels of the path (fp32 compat
 kernel 8 B/px, int8 wire output 2 B/px, inverse 8 B/px), the C3 round-trip
 PEEN/MSE, the C4 16384^2 row-sharded run with its RCCL gather timed
 separately, and the CPU baseline (the oracle, one thread, rank 0, N=1).
@@ -56,6 +69,8 @@ WATCHDOG_EXIT = 3              # exit code when the extras watchdog fired (headl
 HEADLINE_KERNEL_PMC = "fdct_duo_u8_kernel"  # the headline's kernel as profiles/pmc_traffic.json names it
 CEIL_CAPS = (0, 4, 6, 7, 8, 10, 12, 16, 20, 24)  # residency caps (waves per CU) of the copy ceilings; 0 = none
 DONE_FRAC = 0.9                # a kernel at >= this fraction of its copy ceiling is "done"
+DUMP_BUDGET_BYTES = 32 << 20   # --dump-outputs writes at most this much, all ranks together
+DUMP_SEED = 20240607           # seed of the row-band sample of a plane above the budget
 
 
 def sets_for(input_bytes: int, minimum: int = 2) -> int:
@@ -63,6 +78,39 @@ def sets_for(input_bytes: int, minimum: int = 2) -> int:
     >= INPUT_FOOTPRINT: every launch then reads its input from HBM, not from
     the Infinity Cache (which the output stores, non-temporal, do not fill)."""
     return max(minimum, -(-INPUT_FOOTPRINT // max(1, input_bytes)))
+
+
+def dump_rows(rows: int, cols: int, budget_bytes: int, seed: int = DUMP_SEED):
+    """Rows of a rows x cols fp32 plane that --dump-outputs writes: None (the
+    whole plane) if it fits `budget_bytes`, else the rows of a seeded sample
+    of its 8-row tile bands, ascending, as many whole bands as fit (at least
+    one).  A function of its arguments only: the same rows in every run and
+    in every build."""
+    if rows * cols * 4 <= budget_bytes:
+        return None
+    bands = -(-rows // 8)
+    keep = max(1, min(bands, budget_bytes // (8 * cols * 4)))
+    pick = np.sort(np.random.default_rng(seed).choice(bands, size=keep, replace=False))
+    idx = (pick[:, None] * 8 + np.arange(8)[None, :]).reshape(-1)
+    return idx[idx < rows]
+
+
+def dump_outputs(directory, rank, world, plane):
+    """Write `plane` (a 2-D fp32 device tensor: the last timed step's output)
+    or its dump_rows sample as float32 .npy; returns what the line reports."""
+    os.makedirs(directory, exist_ok=True)
+    rows = dump_rows(plane.shape[0], plane.shape[1], DUMP_BUDGET_BYTES // world)
+    if rows is None:
+        arr = plane.cpu().numpy()
+    else:
+        import torch
+        arr = plane[torch.from_numpy(rows).to(plane.device)].cpu().numpy()
+    arr = np.ascontiguousarray(arr, dtype=np.float32)
+    name = "fwd_coefficients" + (f"_rank{rank}" if rank else "")
+    np.save(os.path.join(directory, name + ".npy"), arr)
+    return {"file": name + ".npy", "shape": list(arr.shape), "dtype": "float32",
+            "rows": "all" if rows is None else f"{len(rows)} of {plane.shape[0]}: seeded sample of 8-row bands "
+                                               f"(dump_rows, seed {DUMP_SEED})"}
 
 
 def parse():
@@ -73,6 +121,15 @@ def parse():
     ap.add_argument("--size", type=int, default=8192, help="square frame side (C3: 8192)")
     ap.add_argument("--sets", type=int, default=None,
                     help="rotating buffer sets per GPU (default: inputs total >= 4x the 256 MiB Infinity Cache)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the coefficient plane of the last timed step to "
+                         "DIR/fwd_coefficients.npy (float32; a fixed seeded sample of its 8-row bands above "
+                         f"{DUMP_BUDGET_BYTES >> 20} MiB)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline: the parity spot-check against the oracle, "
+                         "the sustained phase, the extras (other kernels, copy ceilings, C2/C4/C5) and the CPU "
+                         "baseline (--no-*, --sustain-s, --c4-size, --c5-* and --extras-timeout-s select among those and "
+                         "do nothing without --full)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true")
     ap.add_argument("--sustain-s", type=float, default=4.0,
@@ -260,9 +317,14 @@ def main():
     achieved = BYTES_PER_PX["u8_f32"] * px / (kavg * 1e-3) / 1e9  # GB/s per GPU
     kavg_max = max_over_ranks(kavg)
 
+    # what the timed path computed in its last step, for a comparison of builds
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, rank, world, outs[(args.steps - 1) % args.sets])
+
     # parity spot-check of the timed output (set 0) against the oracle
     parity = None
-    if rank == 0:
+    if rank == 0 and args.full:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         try:
             import oracle
@@ -324,7 +386,7 @@ def main():
             "timing": "HIP events around the timed region on the launch stream; avg launch = region / steps",
         },
         "vs_baseline_ref": "T4 14.70 ms (README.md:55) = 4.57 Gpixel/s, fp32-in 3-kernel path",
-        "parity_spot_check": parity,
+        "full": bool(args.full),
         "host_wall_s": round(wall, 4),
         "warmup_lead_in_launches": headline_lead_in,
         # which sources built the library that was timed (src_digest.py): the
@@ -332,13 +394,18 @@ def main():
         "provenance": hpdct.provenance(),
     }
 
+    if dumped:
+        result["dumped_outputs"] = dumped
+    if args.full:
+        result["parity_spot_check"] = parity
+
     # ------------------------------------------------------------ sustained headline
-    if args.sustain_s > 0:
+    if args.full and args.sustain_s > 0:
         result["sustained"] = _sustained(torch, hip, fwd_calls, args.sustain_s, px, world, barrier,
                                          max_over_ranks)
 
     # ------------------------------------------------------------ other kernels of the path
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         extras = {}
         # A hang in the extras (a first multi-GPU run of the RCCL gather, say)
         # must not cost the headline line: the watchdog prints it and exits.
@@ -390,7 +457,7 @@ def main():
                 result["c4_" + key] = c4[key]
 
     # ------------------------------------------------------------ CPU baseline
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = _cpu_baseline(n)
 
     if "extras" in result:

@@ -185,3 +185,35 @@ def test_kernel_status_puts_every_kernel_beside_its_ceiling():
     assert ks["dropin.idct_all_blocks_cublasv2"][2] == round(122 / 133, 3)
     assert ks["c3.one_pass"][3] == "open" and ks["c2_fwd_u8_f32"][3] == "done"
     assert ks["c5_i8_frames_per_s"] == [2500.0, 2800.0, round(2500 / 2800, 3), "open"]
+
+
+def test_plain_run_is_the_default_and_full_is_an_option(monkeypatch):
+    monkeypatch.setattr(sys, "argv", ["bench.py"])
+    args = bench.parse()
+    assert args.full is False and args.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "d"])
+    args = bench.parse()
+    assert args.full is True and args.dump_outputs == "d"
+
+
+def test_dump_rows_is_a_fixed_sample_of_whole_tile_bands_within_the_budget():
+    import numpy as np
+    # a plane within the budget is written whole
+    assert bench.dump_rows(1024, 1024, bench.DUMP_BUDGET_BYTES) is None
+    assert bench.dump_rows(2048, 4096, 2048 * 4096 * 4) is None
+    for rows, cols, budget in ((8192, 8192, bench.DUMP_BUDGET_BYTES), (8192, 8192, bench.DUMP_BUDGET_BYTES // 8),
+                               (16384, 16384, bench.DUMP_BUDGET_BYTES), (1001, 520, 64 << 10), (13, 100000, 1)):
+        idx = bench.dump_rows(rows, cols, budget)
+        assert np.array_equal(idx, bench.dump_rows(rows, cols, budget))  # the same rows every time
+        assert len(idx) > 0 and np.all(np.diff(idx) > 0) and idx[0] >= 0 and idx[-1] < rows
+        # whole 8-row bands (the last band of a ragged plane is short)
+        for b in np.unique(idx // 8):
+            assert np.count_nonzero(idx // 8 == b) == min(8, rows - 8 * b)
+        # within the budget, or the single band that is the least it can write
+        assert len(idx) * cols * 4 <= budget or len(np.unique(idx // 8)) == 1
+    # the headline frame: 128 of its 1024 bands, 32 MiB
+    idx = bench.dump_rows(8192, 8192, bench.DUMP_BUDGET_BYTES)
+    assert len(idx) == 1024 and len(idx) * 8192 * 4 == 32 << 20
+    assert bench.DUMP_BUDGET_BYTES <= 64 * 10**6
+    # another seed, other rows
+    assert not np.array_equal(idx, bench.dump_rows(8192, 8192, bench.DUMP_BUDGET_BYTES, seed=1))

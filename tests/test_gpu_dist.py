@@ -236,7 +236,7 @@ def _free_port():
 def test_bench_nccl_process_group_at_world_size_1(tmp_path):
     env = dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0", LOCAL_WORLD_SIZE="1",
                MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()))
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "5", "--warmup", "2",
            "--size", "2048", "--sets", "4", "--no-cpu-baseline", "--sustain-s", "0", "--c4-size", "2048",
            "--c5-size", "512", "--c5-frames", "8"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
@@ -270,10 +270,43 @@ def test_bench_watchdog_exits_nonzero_after_the_headline_line(tmp_path):
     """when the extras watchdog fires (a hung C4 gather, say), rank 0
     still prints the headline line, with extras.error set, and the process
     exits 3, not 0, so a caller that checks the exit code sees the hang."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "1", "--steps", "5", "--warmup", "2",
            "--size", "2048", "--sets", "4", "--no-cpu-baseline", "--sustain-s", "0", "--extras-timeout-s", "0.5"]
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
     assert r.returncode == 3, r.stdout[-2000:] + r.stderr[-4000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert "watchdog" in line["extras"]["error"] and line["value"] > 0
+
+
+def test_bench_plain_run_is_the_headline_only_and_dumps_its_last_step(tmp_path, hp, dev):
+    """A plain run (no --full) times the headline and nothing else: no extras,
+    sustained phase, CPU baseline or parity spot-check in its line.  With
+    --dump-outputs it writes the coefficient plane of the last timed step:
+    here step 5 of 5 over 2 rotating sets, so set 0, the srand(42) frame, whole
+    (it fits the budget), equal to hpdct.forward of that frame bit for bit."""
+    import numpy as np
+    import torch
+    n, out = 1024, tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "5", "--warmup", "2",
+           "--size", str(n), "--sets", "2", "--dump-outputs", str(out)]
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=ROOT)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout
+    line = json.loads(lines[0])
+    assert line["full"] is False and line["steps"] == 5 and line["warmup"] == 2
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["unit"] == "Gpixel/s" and line["dtype"] == "f32"
+    assert line["higher_is_better"] is True
+    assert line["value"] == pytest.approx(n * n / (line["ms_per_step"] * 1e-3) / 1e9, rel=1e-3)
+    for key in ("extras", "sustained", "cpu_baseline", "parity_spot_check", "kernel_status"):
+        assert key not in line
+    assert line["dumped_outputs"] == {"file": "fwd_coefficients.npy", "shape": [n, n], "dtype": "float32",
+                                      "rows": "all"}
+    assert sorted(os.listdir(out)) == ["fwd_coefficients.npy"]
+    got = np.load(out / "fwd_coefficients.npy")
+    assert got.dtype == np.float32 and got.shape == (n, n)
+    x = torch.from_numpy(hp.fill_rand_u8(n * n, 42).reshape(n, n)).to(dev)
+    want = hp.forward(x).cpu().numpy()
+    assert np.array_equal(got.view(np.uint32), want.view(np.uint32))

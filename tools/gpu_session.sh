@@ -9,11 +9,11 @@
 #   smoke                 __graft_entry__.smoke()
 #   tests                 pytest -m gpu (thread timeout per test)
 #   tests:<expr>          pytest -m gpu -k <expr>
-#   bench                 the driver's exact bench command
+#   bench                 the whole bench: bench.py --full --gpus 1 --steps 20 --warmup 5
 #   prof                  the same under rocprofv3 --kernel-trace --stats, plus
 #                         tools/trace_summary.py over its kernel trace
 #   shard                 benchmark_hpdct 16384 --gpus 1 (fp32 and int8)
-#   n2                    bench.py --gpus 2 --backend gloo (two ranks, one GPU)
+#   n2                    bench.py --full --gpus 2 --backend gloo (two ranks, one GPU)
 #   kb:<args>             tools/kbench3 with <args> (':' separated), e.g.
 #                         kb:8192:64:3:occsz:16 -> log kb3_occsz_8192.log
 #   pmcsq:<args>          SQ/GRBM counter pass over kbench3 <args>
@@ -56,7 +56,7 @@ pmc() {  # pmc <name> <counters> <kbench3 args...>: a counter-only pass, its own
     echo "== pmc $name rc=$rc" | tee -a "$OUT/steps.log"
     return $rc
 }
-bench_cmd=(python3 bench.py --gpus 1 --steps 20 --warmup 5)
+bench_cmd=(python3 bench.py --full --gpus 1 --steps 20 --warmup 5)
 
 for s in "$@"; do
     IFS=: read -r -a p <<< "$s"
@@ -80,7 +80,7 @@ for s in "$@"; do
     shard)
         step shard_f32 120 cuda-dct-idct_amd/bin/benchmark_hpdct 16384 5 --gpus 1 || exit $?
         step shard_i8 120 cuda-dct-idct_amd/bin/benchmark_hpdct 16384 5 --gpus 1 --int8 || exit $? ;;
-    n2) step bench_n2_gloo 600 python3 bench.py --gpus 2 --backend gloo --steps 20 --warmup 5 --no-cpu-baseline \
+    n2) step bench_n2_gloo 600 python3 bench.py --full --gpus 2 --backend gloo --steps 20 --warmup 5 --no-cpu-baseline \
             || exit $? ;;
     kb) step "kb3_${p[4]}_${p[1]}" 300 tools/kbench3 "${p[@]:1}" || exit $? ;;
     pmcsq) pmc "sq_${p[4]}_${p[1]}" "$SQ" "${p[@]:1}" || exit $? ;;
