@@ -1,6 +1,6 @@
 // hpdct_decode.hip -- launcher of hpdct_decode_i8_f32 (kernel: hpdct_decode.hpp).
 #include "hpdct_decode.hpp"
-#include "hpdct_launch.hpp"
+#include "hpdct_residency.hpp"
 
 namespace hpdct {
 
@@ -14,12 +14,10 @@ constexpr uint32_t kDecodeCapWaves = 12;
 hipError_t launch_decode_i8_f32(const int8_t* in, float* out, uint64_t n, hipStream_t s) {
     if (n == 0) return hipSuccess;
     constexpr int kB = 64, kU = 1;
-    auto* kern = decode_i8_f32_kernel<kB, kU, false>;
-    static const size_t dyn = residency_cap_lds(static_lds_of(kern), kDecodeCapWaves);
     const uint64_t blocks = decode_blocks<kB, kU>(n, 0);
     if (blocks > 0x7fffffffull) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(kern, dim3(static_cast<uint32_t>(blocks)), dim3(kB), dyn, s, in, out, n);
-    return hipGetLastError();
+    return launch_capped<decode_i8_f32_kernel<kB, kU, false>>(dim3(static_cast<uint32_t>(blocks)), dim3(kB),
+                                                              kDecodeCapWaves, s, in, out, n);
 }
 
 }  // namespace hpdct

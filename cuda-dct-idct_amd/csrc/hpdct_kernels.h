@@ -10,6 +10,62 @@ namespace hpdct {
 
 constexpr uint32_t kBlockThreads = 256;  // 4 wave64 per workgroup
 
+// Compile-time kernel variants (bit flags) of the product kernels.  Bits not
+// listed here are the tools' A/B variants (tools/kbench_variants.hpp).
+enum : unsigned {
+    kVarFastDiv = 1u,  // quotient by  q0=c*r; e=fma(-q0,Q,c); q=fma(e,r,q0)  (r = RN(1/Q)).  Gives the same
+                       // roundf() as IEEE c/Q for every |c| <= 4096 and every integer Q in 1..255
+                       // (exhaustive: tests/tools/verify_fastdiv.*); enabled unconditionally only for such
+                       // tables with uint8 input and the built-in T (|C| <= 1024); fp32 input with such a
+                       // table takes it per output row under kVarFastDivChecked.
+    kVarLdsStore = 8u, // fp32 rows re-staged through LDS so every store instruction writes 1 KiB contiguous
+    kVarNT = 16u,      // non-temporal (streaming) stores for the output planes
+    // bits 12..13: workgroup size: 0 -> 256 threads, 1 -> 64, 2 -> 512, 3 -> 1024
+    kVarRowFirst = 1u << 14,  // cublasDCTv2 pass order (row pass first), fp32 compat path
+    kVarWbDequant = 1u << 15, // inverse: write q*Q back into the fp32 coefficient input
+                              // (in-place multiply_matrices of main_cublass_2.cu:285)
+    kVarFastDivChecked = 1u << 26,  // fp32 input (any T), integer table in 1..255: the 3-op quotient for an
+                                    // output row when every lane's 8 values have |C| <= 4096 (wave-uniform
+                                    // test, NaN/inf fail it), IEEE division otherwise: exact either way
+                                    // (verify_fastdiv covers every |C| <= 4096)
+    kVarPacked = 1u << 19,    // uint8 -> fp32 or int8 quantised, built-in T: packed-fp32 transform and
+                              // quotient (fdct_tile_pk; fp32: 844 instead of 1,308 VALU instructions per set)
+    kVarI8Pack = 1u << 17,    // int8 output: round-half-away folded into the truncating cvt, and each
+                              // coefficient converted straight into its byte (SDWA dst_sel, one op)
+    kVarJpegQ = 1u << 11,     // the DEFAULT JPEG table, uint8 input, built-in T, level shift 128 (with
+                              // kVarFastDiv): per position the 3-op form F or H where it is proven exact
+                              // below that position's |C| bound, the 6-op form elsewhere
+                              // (hpdct_quant_forms.h, tests/tools/verify_quant_pos.c)
+    kVarHoistRun = 1u << 20,  // packed u8 -> fp32 forward (the capped headline kernel): the whole-run test
+                              // (split == 64) taken once per set, two straight-line copies of the body, and in
+                              // the whole-run copy each row's re-staged stores issued one row later, after the
+                              // next row's LDS writes (tools/kbench3 group hoist: 56.5 against 57.4-57.7 us)
+    kVarStraddle = 1u << 30,  // fp32 LDS-staged rows: a 64-tile set that straddles two tile rows (width not a
+                              // multiple of 512 px) stores two contiguous runs per instruction instead of
+                              // 32 B per lane; launched only for such widths (the branch costs the
+                              // power-of-two frames ~3 %, profiles/r01/ab_straddle.log)
+};
+// the octet kernels' own variant bit (hpdct_octet.hpp)
+enum : unsigned {
+    kOctRestage = 1u << 20,  // octet output rows re-staged through LDS: each store instruction writes
+                             // four 256-B runs (a whole row of the wave's 8 tiles each) instead of
+                             // 16-B pieces at a 32-B stride
+};
+// Bits only the product kernels give a meaning to: the tools' A/B variant
+// bits must stay clear of them (static_assert in tools/kbench_variants.hpp).
+constexpr unsigned kProductOnlyVarBits = kVarFastDivChecked | kVarJpegQ;
+constexpr uint32_t block_of(unsigned var) {
+    return ((var >> 12) & 3u) == 1u ? 64u : ((var >> 12) & 3u) == 2u ? 512u : ((var >> 12) & 3u) == 3u ? 1024u : kBlockThreads;
+}
+template <unsigned kVar>
+constexpr uint32_t kBlock = block_of(kVar);
+// kV with its workgroup-size bits set for kThreads threads
+template <uint32_t kThreads>
+constexpr unsigned with_block(unsigned kV) {
+    static_assert(kThreads == 64 || kThreads == 256 || kThreads == 512 || kThreads == 1024, "workgroup size");
+    return (kV & ~(3u << 12)) | ((kThreads == 64 ? 1u : kThreads == 512 ? 2u : kThreads == 1024 ? 3u : 0u) << 12);
+}
+
 // 64 floats passed by value as a kernel argument (lands in SGPRs)
 struct Mat64 {
     float v[64];
@@ -21,6 +77,8 @@ struct QParams {
     Mat64 q;
     Mat64 r;
 };
+
+namespace policy { struct Choice; }  // what a call launches (hpdct_policy.hpp)
 
 // Tile geometry of one launch: ntiles = (height/8) * (width/8) < 2^32.
 struct TileGrid {
@@ -62,39 +120,36 @@ enum : int { kRtReconNone = 0, kRtReconU8 = 1, kRtReconF32 = 2 };
 // it into *sums (a memset of *sums and the tile kernel when no slot can be had).
 hipError_t launch_roundtrip(const uint8_t* img, float* coef, void* recon, int recon_kind, RtSums* sums,
                             const TileGrid& g, const QParams& qp, int fast, bool zero_sums, hipStream_t s);
-// The pieces launch_roundtrip (hpdct_roundtrip.hip) chooses from:
+// The pieces launch_roundtrip (hpdct_roundtrip.hip) launches as policy::roundtrip chose (c):
 //  - the tile-per-lane kernels, one unit per reconstruction kind
 //    (hpdct_rt_tile_{u8,f32,none}.hip); sums: the struct (or spread
 //    sub-slot 0) the workgroups add into, or nullptr;
-//  - the two-lanes-per-tile kernel (hpdct_rt_duo.hip): fast 1 or 2, a uint8
-//    reconstruction (recon) or none (nullptr); spread: a zeroed spread slot
+//  - the two-lanes-per-tile kernel (hpdct_rt_duo.hip): the verified quotient, a
+//    uint8 reconstruction (recon) or none (nullptr); spread: a zeroed spread slot
 //    (kRtSpread sub-slots, hpdct_roundtrip.hpp) the waves add into, or
 //    nullptr for no sums;
 //  - the finish kernel folding a spread slot into *dst (overwrite, or add
 //    when accumulate) and zeroing it.
 hipError_t launch_rt_tile_u8(const uint8_t* img, float* coef, void* recon, RtSums* sums, const TileGrid& g,
-                             const QParams& qp, int fast, hipStream_t s);
+                             const QParams& qp, const policy::Choice& c, hipStream_t s);
 hipError_t launch_rt_tile_f32(const uint8_t* img, float* coef, void* recon, RtSums* sums, const TileGrid& g,
-                              const QParams& qp, int fast, hipStream_t s);
+                              const QParams& qp, const policy::Choice& c, hipStream_t s);
 hipError_t launch_rt_tile_none(const uint8_t* img, float* coef, void* recon, RtSums* sums, const TileGrid& g,
-                               const QParams& qp, int fast, hipStream_t s);
+                               const QParams& qp, const policy::Choice& c, hipStream_t s);
 hipError_t launch_rt_duo(const uint8_t* img, float* coef, void* recon, int recon_kind, unsigned long long* spread,
-                         const TileGrid& g, const QParams& qp, int fast, hipStream_t s);
+                         const TileGrid& g, const QParams& qp, const policy::Choice& c, hipStream_t s);
 hipError_t launch_rt_duo_f32(const uint8_t* img, float* coef, void* recon, unsigned long long* spread,
-                             const TileGrid& g, const QParams& qp, int fast, hipStream_t s);
+                             const TileGrid& g, const QParams& qp, const policy::Choice& c, hipStream_t s);
 hipError_t launch_rt_finish(RtSums* dst, unsigned long long* spread, bool accumulate, hipStream_t s);
 // the spread slot of a sums pointer back to its device's free list
 // (hpdct_roundtrip_release_sums); false when the pointer had none
 bool release_sums_slot(const void* sums);
 
 // uint8 -> quantised fp32 forward on the two-lanes-per-tile mapping (round 6;
-// fdct_duo_u8_kernel, hpdct_rt_duo.hpp): qmode 1 or 2, built-in T, level
-// shift 128, tiles_x a multiple of 32, width below 2^22 px.  kDuoFwdBlock-thread
-// workgroups, at most kDuoFwdCapWgs resident per CU (16 waves); AUTO takes it
-// from kDuoFwdMinWavesPerCU of its 32-tile waves per CU (launch_fdct_impl).
-constexpr uint32_t kDuoFwdBlock = 256, kDuoFwdCapWgs = 4, kDuoFwdMinWavesPerCU = 4;
-hipError_t launch_fdct_duo_u8(const uint8_t* img, float* coef, const TileGrid& g, const QParams& qp, int qmode,
-                              hipStream_t s);
+// fdct_duo_u8_kernel, hpdct_rt_duo.hpp), as policy::forward chose it (c):
+// built-in T, level shift 128, tiles_x a multiple of 32, width below 2^22 px.
+hipError_t launch_fdct_duo_u8(const uint8_t* img, float* coef, const TileGrid& g, const QParams& qp,
+                              const policy::Choice& c, hipStream_t s);
 
 // A list of frames per launch (hpdct_forward_frames): up to kMaxFramesPerLaunch
 // device pointer pairs travel in the kernel arguments (1 KiB).
@@ -109,10 +164,9 @@ struct FrameTable {
 template <typename TOut>
 hipError_t launch_fdct_frames(const FrameTable<TOut>& ft, int n, const TileGrid& g, const QParams& q, int qmode,
                               hipStream_t s);
-// the duo forward over such a list (fp32 out; the conditions of
-// launch_fdct_duo_u8, the size rule on the whole list)
-hipError_t launch_fdct_duo_u8_frames(const FrameTable<float>& ft, int n, const TileGrid& g, const QParams& qp,
-                                     int qmode, hipStream_t s);
+// the duo forward over such a list (fp32 out; c.grid_y frames)
+hipError_t launch_fdct_duo_u8_frames(const FrameTable<float>& ft, const TileGrid& g, const QParams& qp,
+                                     const policy::Choice& c, hipStream_t s);
 
 hipError_t launch_fill_hash(uint8_t* out, uint64_t n, uint64_t seed, uint64_t first, hipStream_t s);
 
@@ -127,7 +181,7 @@ hipError_t launch_floor_probe(int kind, const uint8_t* in, float* out, const Til
 hipError_t launch_copy_ceiling(const void* in, int in_bytes, void* o0, int o0_bytes, void* o1, int o1_bytes,
                                uint64_t n, uint32_t cap_waves, hipStream_t s);
 
-// hpdct_mapping in force (0 auto, 1 tile, 2 octet); hpdct_api.cpp.
+// hpdct_mapping in force (0 auto, 1 tile, 2 octet, 3 duo); hpdct_api.cpp.
 int mapping_mode();
 
 // Records msg as hpdct_last_error_string() of this thread and returns st

@@ -11,7 +11,7 @@
 //     bytes (8 per set),
 //   - each fp32 row store is two global_store_dwordx4 that together cover
 //     2 KiB contiguous.
-// Only the variants the library launches live here (hpdct_launch.hpp); the
+// Only the variants the library launches live here (hpdct_policy.hpp); the
 // measured-and-rejected A/B variants and the phase-split diagnostics are in
 // the tools-only tools/kbench_variants.hpp.
 // Why not one wavefront per tile: a lane-per-pixel mapping needs 7 cross-lane
@@ -24,50 +24,6 @@
 #include "hpdct_tile.hpp"
 
 namespace hpdct {
-
-// Compile-time kernel variants (bit flags) of the product kernels.  Bits not
-// listed here are the tools' A/B variants (tools/kbench_variants.hpp).
-enum : unsigned {
-    kVarFastDiv = 1u,  // quotient by  q0=c*r; e=fma(-q0,Q,c); q=fma(e,r,q0)  (r = RN(1/Q)).  Gives the same
-                       // roundf() as IEEE c/Q for every |c| <= 4096 and every integer Q in 1..255
-                       // (exhaustive: tests/tools/verify_fastdiv.*); enabled unconditionally only for such
-                       // tables with uint8 input and the built-in T (|C| <= 1024); fp32 input with such a
-                       // table takes it per output row under kVarFastDivChecked.
-    kVarLdsStore = 8u, // fp32 rows re-staged through LDS so every store instruction writes 1 KiB contiguous
-    kVarNT = 16u,      // non-temporal (streaming) stores for the output planes
-    // bits 12..13: workgroup size: 0 -> 256 threads, 1 -> 64, 2 -> 512, 3 -> 1024
-    kVarRowFirst = 1u << 14,  // cublasDCTv2 pass order (row pass first), fp32 compat path
-    kVarWbDequant = 1u << 15, // inverse: write q*Q back into the fp32 coefficient input
-                              // (in-place multiply_matrices of main_cublass_2.cu:285)
-    kVarFastDivChecked = 1u << 26,  // fp32 input (any T), integer table in 1..255: the 3-op quotient for an
-                                    // output row when every lane's 8 values have |C| <= 4096 (wave-uniform
-                                    // test, NaN/inf fail it), IEEE division otherwise: exact either way
-                                    // (verify_fastdiv covers every |C| <= 4096)
-    kVarPacked = 1u << 19,    // uint8 -> fp32 or int8 quantised, built-in T: packed-fp32 transform and
-                              // quotient (fdct_tile_pk; fp32: 844 instead of 1,308 VALU instructions per set)
-    kVarI8Pack = 1u << 17,    // int8 output: round-half-away folded into the truncating cvt, and each
-                              // coefficient converted straight into its byte (SDWA dst_sel, one op)
-    kVarJpegQ = 1u << 11,     // the DEFAULT JPEG table, uint8 input, built-in T, level shift 128 (with
-                              // kVarFastDiv): per position the 3-op form F or H where it is proven exact
-                              // below that position's |C| bound, the 6-op form elsewhere
-                              // (hpdct_quant_forms.h, tests/tools/verify_quant_pos.c)
-    kVarHoistRun = 1u << 20,  // packed u8 -> fp32 forward (the capped headline kernel): the whole-run test
-                              // (split == 64) taken once per set, two straight-line copies of the body, and in
-                              // the whole-run copy each row's re-staged stores issued one row later, after the
-                              // next row's LDS writes (tools/kbench3 group hoist: 56.5 against 57.4-57.7 us)
-    kVarStraddle = 1u << 30,  // fp32 LDS-staged rows: a 64-tile set that straddles two tile rows (width not a
-                              // multiple of 512 px) stores two contiguous runs per instruction instead of
-                              // 32 B per lane; launched only for such widths (the branch costs the
-                              // power-of-two frames ~3 %, profiles/r01/ab_straddle.log)
-};
-// Bits only the product kernels give a meaning to: the tools' A/B variant
-// bits must stay clear of them (static_assert in tools/kbench_variants.hpp).
-constexpr unsigned kProductOnlyVarBits = kVarFastDivChecked | kVarJpegQ;
-template <unsigned kVar>
-constexpr uint32_t kBlock = ((kVar >> 12) & 3u) == 1u   ? 64u
-                            : ((kVar >> 12) & 3u) == 2u ? 512u
-                            : ((kVar >> 12) & 3u) == 3u ? 1024u
-                                                        : kBlockThreads;
 
 namespace {
 
@@ -143,23 +99,6 @@ __device__ __forceinline__ float quotient(float c, float q, float r) {
         (void)r;
         return c / q;
     }
-}
-
-// int8 coefficients: round-half-away(d) = trunc(d + copysign(0.49999997, d))
-// and v_cvt_i32_f32 truncates, so the trunc is folded into the conversion;
-// each conversion writes its byte of the packed dword directly (SDWA dst_sel).
-__device__ __forceinline__ uint32_t pack_q_i8x4(float a, float b, float c, float d) {
-    auto biased = [](float x) { return x + signed_half(x); };
-    uint32_t w;
-    asm volatile("v_cvt_i32_f32_sdwa %0, %1 dst_sel:BYTE_0 dst_unused:UNUSED_PAD src0_sel:DWORD"
-                 : "=v"(w) : "v"(biased(a)));
-    asm volatile("v_cvt_i32_f32_sdwa %0, %1 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD"
-                 : "+v"(w) : "v"(biased(b)));
-    asm volatile("v_cvt_i32_f32_sdwa %0, %1 dst_sel:BYTE_2 dst_unused:UNUSED_PRESERVE src0_sel:DWORD"
-                 : "+v"(w) : "v"(biased(c)));
-    asm volatile("v_cvt_i32_f32_sdwa %0, %1 dst_sel:BYTE_3 dst_unused:UNUSED_PRESERVE src0_sel:DWORD"
-                 : "+v"(w) : "v"(biased(d)));
-    return w;
 }
 
 // v_cvt_i32_f32 (truncating) of an already-biased value straight into byte
@@ -429,8 +368,7 @@ __device__ __forceinline__ void store_row_lds2(float4* __restrict__ slot, float*
 // and whose other 64-k start the next (RowSink derives that segment); 0 for a
 // ragged last set or a set over more than two tile rows (per-lane stores).
 template <unsigned kVar, typename TIn, typename Body>
-__device__ __forceinline__ void walk_sets(const TIn* __restrict__ src, const TileGrid& g, float4* slots, Body&& body) {
-    (void)slots;
+__device__ __forceinline__ void walk_sets(const TIn* __restrict__ src, const TileGrid& g, Body&& body) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(blockIdx.x * (kBlock<kVar> / 64u) + threadIdx.x / 64u);
     const uint32_t nsets = (g.ntiles + 63u) / 64u;
@@ -572,7 +510,7 @@ __device__ __forceinline__ void fdct_packed_body(const uint8_t* __restrict__ img
                                                  const TileGrid& g, float shift, BQuot2&& bquot2) {
     float4* const slots = wave_slots<kVar>();
     const RowSink<kVar, float> sink{reinterpret_cast<float*>(out), g.width, slots};
-    walk_sets<kVar>(img, g, slots, [&](const RawTile<uint8_t>& raw, const TilePos& p, uint32_t ok, uint64_t seg) {
+    walk_sets<kVar>(img, g, [&](const RawTile<uint8_t>& raw, const TilePos& p, uint32_t ok, uint64_t seg) {
       auto work = [&](auto whole_run) {
         // whole runs: each row's two re-staged float4 are stored one row later,
         // so the LDS read's latency hides under the next row's arithmetic
@@ -672,7 +610,7 @@ __device__ __forceinline__ void fdct_body(const TIn* __restrict__ img, TOut* __r
     const RowSink<kVar, TOut> sink{out, g.width, slots};
     const RowSink<kVar, float> wb_sink{shifted, g.width, slots};
 
-    walk_sets<kVar>(img, g, slots, [&](const RawTile<TIn>& raw, const TilePos& p, uint32_t ok, uint64_t seg) {
+    walk_sets<kVar>(img, g, [&](const RawTile<TIn>& raw, const TilePos& p, uint32_t ok, uint64_t seg) {
         fdct_tile_body<TIn, TOut, kQuant, kWriteback, kVar>(raw, p, ok, seg, T, sink, wb_sink, out, g, qp, shift);
     });
 }
@@ -718,7 +656,7 @@ __global__ __launch_bounds__(kBlock<kVar>, 1) void idct_kernel(const TIn* __rest
     const RowSink<kVar, TOut> sink{out, g.width, slots};
     const RowSink<kVar, float> dq_sink{dq_out, g.width, slots};
 
-    walk_sets<kVar>(coef, g, slots, [&](const RawTile<TIn>& raw, const TilePos& p, uint32_t ok, uint64_t seg) {
+    walk_sets<kVar>(coef, g, [&](const RawTile<TIn>& raw, const TilePos& p, uint32_t ok, uint64_t seg) {
         float d[8][8];
         raw.to_float(d, 0.0f);
         if constexpr (kDequant) {
@@ -739,33 +677,6 @@ __global__ __launch_bounds__(kBlock<kVar>, 1) void idct_kernel(const TIn* __rest
             idct_tile(T, d, emit);
         }
     });
-}
-
-// ---------------------------------------------------------------------------
-// Synthetic frame generator (config C4): 16 pixels per lane.
-// ---------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t hash_px(uint64_t seed, uint64_t idx) {
-    uint64_t z = seed + (idx + 1) * 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return static_cast<uint32_t>((z ^ (z >> 31)) & 255u);
-}
-
-[[maybe_unused]] static __global__ __launch_bounds__(kBlockThreads) void fill_hash_kernel(uint8_t* __restrict__ out, uint64_t n,
-                                                                         uint64_t seed, uint64_t first) {
-    const uint64_t i0 = (static_cast<uint64_t>(blockIdx.x) * kBlockThreads + threadIdx.x) * 16u;
-    if (i0 >= n) return;
-    if (i0 + 16 <= n) {
-        uint32_t w[4];
-        unroll<4>([&](auto k) {
-            uint32_t acc = 0;
-            unroll<4>([&](auto b) { acc |= hash_px(seed, first + i0 + k * 4 + b) << (8 * b); });
-            w[k] = acc;
-        });
-        *reinterpret_cast<uint4*>(out + i0) = make_uint4(w[0], w[1], w[2], w[3]);
-    } else {
-        for (uint64_t i = i0; i < n; ++i) out[i] = static_cast<uint8_t>(hash_px(seed, first + i));
-    }
 }
 
 }  // namespace hpdct

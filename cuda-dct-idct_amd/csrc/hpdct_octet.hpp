@@ -29,12 +29,6 @@
 
 namespace hpdct {
 
-enum : unsigned {
-    kOctRestage = 1u << 20,  // octet output rows re-staged through LDS: each store instruction writes
-                             // four 256-B runs (a whole row of the wave's 8 tiles each) instead of
-                             // 16-B pieces at a 32-B stride
-};
-
 namespace {
 
 constexpr uint32_t kOctStride = 72;  // floats per tile in the exchange slot

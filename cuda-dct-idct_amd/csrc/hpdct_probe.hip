@@ -92,10 +92,8 @@ __global__ __launch_bounds__(64) void copy_ceiling_kernel(const void* in, void* 
 
 template <int kIn, int kO0, int kO1>
 hipError_t copy_ceiling_go(const void* in, void* o0, void* o1, uint64_t n, uint32_t cap_waves, hipStream_t s) {
-    const size_t dyn = residency_cap_lds(0, cap_waves);
-    hipLaunchKernelGGL((copy_ceiling_kernel<kIn, kO0, kO1>), dim3(static_cast<uint32_t>(n / kCeilPx)), dim3(64), dyn,
-                       s, in, o0, o1);
-    return hipGetLastError();
+    return launch_capped<copy_ceiling_kernel<kIn, kO0, kO1>>(dim3(static_cast<uint32_t>(n / kCeilPx)), dim3(64),
+                                                             cap_waves, s, in, o0, o1);
 }
 
 template <int kIn, int kO0>
@@ -120,34 +118,15 @@ hipError_t launch_copy_ceiling(const void* in, int in_bytes, void* o0, int o0_by
                          : copy_ceiling_o1<4, 4>(in, o0, o1, o1_bytes, n, cap_waves, s);
 }
 
-// The (grid, workgroup) the uint8 -> fp32 forward with the default table
-// launches for g (launch_fdct_impl -> launch_fdct_duo_u8 / fdct_octet_go /
-// fdct_tile_go), without its residency cap.
-void forward_u8_f32_shape(const TileGrid& g, dim3& grid, dim3& block) {
-    if (duo_fwd_u8_fits(g)) {
-        const uint32_t waves = (g.ntiles + 31u) / 32u, per = kDuoFwdBlock / 64u;
-        grid = dim3((waves + per - 1u) / per), block = dim3(kDuoFwdBlock);
-        return;
-    }
-    if (pick_mapping(g, false) == Mapping::kOctet) {
-        constexpr unsigned kV = kOctVar<float>;
-        grid = octet_grid(g, kBlock<kV>), block = dim3(kBlock<kV>);
-        return;
-    }
-    const uint32_t sets_per_cu = ((g.ntiles + 63u) / 64u + device_cus() - 1u) / device_cus();
-    const uint32_t b = sets_per_cu <= kBigWgSetsPerCU ? 1024u : 64u;
-    grid = grid_for(g, false, 0, b), block = dim3(b);
-}
-
+// On the (grid, workgroup) policy::forward gives the uint8 -> fp32 forward of
+// g with the default table, without its residency cap.
 hipError_t launch_floor_probe(int kind, const uint8_t* in, float* out, const TileGrid& g, hipStream_t s) {
-    dim3 grid, block;
-    forward_u8_f32_shape(g, grid, block);
-    if (kind == 0) {
-        hipLaunchKernelGGL(floor_empty_kernel, grid, block, 0, s);
-    } else {
-        hipLaunchKernelGGL(floor_copy_kernel, grid, block, 0, s, in, out, static_cast<uint64_t>(g.ntiles) * 64u);
-    }
-    return hipGetLastError();
+    policy::Call pc;
+    pc.g = g, pc.qmode = 2, pc.cus = device_cus(), pc.mapping = mapping_mode();
+    const policy::Choice c = policy::forward(pc);
+    const dim3 grid(c.grid_x), block(c.block);
+    if (kind == 0) return launch_capped<floor_empty_kernel>(grid, block, 0, s);
+    return launch_capped<floor_copy_kernel>(grid, block, 0, s, in, out, static_cast<uint64_t>(g.ntiles) * 64u);
 }
 
 }  // namespace hpdct

@@ -1,7 +1,6 @@
 // hpdct_residency.hpp -- residency caps by dynamic-LDS reservation (round 3):
 // the device attributes the caps read and the reservation that leaves room for
-// at most k workgroups per CU.  Shared by the launch choice (hpdct_launch.hpp)
-// and the round-trip / duo-forward launchers (hpdct_rt_duo.hip).
+// at most k workgroups per CU, and the one launch helper every launcher uses.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -47,10 +46,23 @@ inline size_t residency_cap_lds(size_t static_bytes, uint32_t wgs) {
     const size_t per = (device_lds_per_cu() / wgs) & ~static_cast<size_t>(511);
     return per > static_bytes ? per - static_bytes : 0;
 }
-template <typename K>
-size_t static_lds_of(K kern) {
-    hipFuncAttributes a{};
-    return hipFuncGetAttributes(&a, reinterpret_cast<const void*>(kern)) == hipSuccess ? a.sharedSizeBytes : 0;
+
+// Every launch of the library: kKern on (grid, block) with at most cap_wgs
+// resident workgroups per CU (0: the hardware's default, no reservation).  The
+// kernel's static LDS is queried once per kernel and process.
+template <auto kKern, typename... Args>
+hipError_t launch_capped(dim3 grid, dim3 block, uint32_t cap_wgs, hipStream_t s, const Args&... args) {
+    size_t dyn = 0;
+    if (cap_wgs != 0) {
+        static const size_t st = [] {
+            hipFuncAttributes a{};
+            const auto* k = reinterpret_cast<const void*>(kKern);
+            return hipFuncGetAttributes(&a, k) == hipSuccess ? a.sharedSizeBytes : size_t(0);
+        }();
+        dyn = residency_cap_lds(st, cap_wgs);
+    }
+    hipLaunchKernelGGL(kKern, grid, block, dyn, s, args...);
+    return hipGetLastError();
 }
 
 }  // namespace hpdct

@@ -113,46 +113,39 @@ bool release_sums_slot(const void* sums) {
 namespace {
 
 hipError_t tile(const uint8_t* img, float* coef, void* recon, int recon_kind, RtSums* sums, const TileGrid& g,
-                const QParams& qp, int fast, hipStream_t s) {
+                const QParams& qp, const policy::Choice& c, hipStream_t s) {
     switch (recon_kind) {
-        case kRtReconU8: return launch_rt_tile_u8(img, coef, recon, sums, g, qp, fast, s);
-        case kRtReconF32: return launch_rt_tile_f32(img, coef, recon, sums, g, qp, fast, s);
-        default: return launch_rt_tile_none(img, coef, nullptr, sums, g, qp, fast, s);
+        case kRtReconU8: return launch_rt_tile_u8(img, coef, recon, sums, g, qp, c, s);
+        case kRtReconF32: return launch_rt_tile_f32(img, coef, recon, sums, g, qp, c, s);
+        default: return launch_rt_tile_none(img, coef, nullptr, sums, g, qp, c, s);
     }
 }
 
 }  // namespace
 
-// The kernel: the two-lanes-per-tile round trip (hpdct_rt_duo.hpp) for the
-// verified quotient (fast 1 or 2) with any reconstruction, when its sums (if
-// any) have a spread slot, the width is a multiple of 256 pixels (whole
-// 32-tile runs per wave) and the mapping is not forced to "tile"; 8192^2
-// with sums and a uint8 reconstruction 74.3-74.8 us against 78.4 for the
-// tile kernel with the same sums path, without sums 67.0 against 76.8
-// (tools/kb_rt, profiles/r05/f/).  Otherwise the tile-per-lane kernel (IEEE
-// division, ragged widths, forced tile mapping), with its sums in the spread
-// slot's sub-slot 0 when it has one.  The duo kernel addresses a wave's rows
-// with 32-bit byte offsets from the wave's base (DuoAddr, 2 k width + 4 lane
-// fp32 words), which stay below 2^32 for widths below 2^22 pixels; wider
-// frames take the tile kernel.
+// The kernel is policy::roundtrip's choice (hpdct_policy.hpp): the
+// two-lanes-per-tile round trip or the tile-per-lane kernel, the latter with
+// its sums in the spread slot's sub-slot 0 when it has one.
 hipError_t launch_roundtrip(const uint8_t* img, float* coef, void* recon, int recon_kind, RtSums* sums,
                             const TileGrid& g, const QParams& qp, int fast, bool zero_sums, hipStream_t s) {
     int dev = -1;
     unsigned long long* slot = nullptr;
     if (sums && hipGetDevice(&dev) == hipSuccess) slot = slot_for(dev, sums, s);
-    const bool duo = fast != 0 && (!sums || slot) && g.tiles_x % 32u == 0u && g.width < (uint64_t(1) << 22) &&
-                     mapping_mode() != HPDCT_MAPPING_TILE;
+    policy::RtCall pc;
+    pc.g = g, pc.recon = recon_kind, pc.sums = sums != nullptr, pc.slot = slot != nullptr, pc.qmode = fast;
+    pc.cus = device_cus(), pc.mapping = mapping_mode();
+    const policy::Choice c = policy::roundtrip(pc);
     hipError_t e;
-    if (duo) {
-        e = launch_rt_duo(img, coef, recon_kind == kRtReconNone ? nullptr : recon, recon_kind, slot, g, qp, fast, s);
+    if (c.family != policy::Family::kRtTile) {
+        e = launch_rt_duo(img, coef, recon_kind == kRtReconNone ? nullptr : recon, recon_kind, slot, g, qp, c, s);
     } else if (slot) {
-        e = tile(img, coef, recon, recon_kind, reinterpret_cast<RtSums*>(slot), g, qp, fast, s);
+        e = tile(img, coef, recon, recon_kind, reinterpret_cast<RtSums*>(slot), g, qp, c, s);
     } else {
         if (sums && zero_sums) {
             e = hipMemsetAsync(sums, 0, sizeof(RtSums), s);
             if (e != hipSuccess) return e;
         }
-        return tile(img, coef, recon, recon_kind, sums, g, qp, fast, s);
+        return tile(img, coef, recon, recon_kind, sums, g, qp, c, s);
     }
     if (e == hipSuccess && slot) e = launch_rt_finish(sums, slot, !zero_sums, s);
     if (e != hipSuccess && slot) recover_slot(dev, sums, slot, s);

@@ -34,6 +34,8 @@
 #pragma once
 
 #include "hpdct_kernels_impl.hpp"
+#include "hpdct_policy.hpp"
+#include "hpdct_residency.hpp"
 
 namespace hpdct {
 
@@ -134,7 +136,7 @@ constexpr int kRtWaves = kRecon == kRtReconF32 ? 2 : 4;
 // kBlock: threads per workgroup.  256 since round 4 (8192^2, u8 recon: 77.9-78.3
 // against 78.6-80.7 us with sums, 68.8 against 70.8 without, 1024: 87.0;
 // profiles/r04/b/kb3_jqrtb_8192.log)
-constexpr int kRtBlock = 256;
+constexpr int kRtBlock = policy::kRtBlock;
 template <int kRecon, bool kStats, int kQMode, int kRaw = 2, bool kStraddle = false, int kBlock = kRtBlock>
 __global__ __launch_bounds__(kBlock, kRtWaves<kRecon>) void roundtrip_kernel(const uint8_t* __restrict__ img,
                                                                           float* __restrict__ coef,
@@ -166,7 +168,7 @@ __global__ __launch_bounds__(kBlock, kRtWaves<kRecon>) void roundtrip_kernel(con
     }
     const uint32_t lane = threadIdx.x & 63u;
 
-    walk_sets<kVar>(img, g, slots, [&](const RawTile<uint8_t>& raw, const TilePos& p, uint32_t ok, uint64_t seg) {
+    walk_sets<kVar>(img, g, [&](const RawTile<uint8_t>& raw, const TilePos& p, uint32_t ok, uint64_t seg) {
         if constexpr (kStats && kRaw == 2) unroll<8>([&](auto i) { stash[i * 64u + lane] = raw.r[i]; });
         float x[8][8];
         raw.to_float_minus128(x);  // sub_matrix_scalar (utils_kernels.cu:16), exact: (int8)(b ^ 0x80)
@@ -325,34 +327,22 @@ inline dim3 roundtrip_grid(const TileGrid& g, uint32_t block = kRtBlock) {
 }
 
 namespace rt_detail {
-template <int kRecon, bool kStats, int kQMode>
-hipError_t go(const uint8_t* img, float* coef, void* recon, RtSums* sums, const TileGrid& g, const QParams& qp,
-              hipStream_t s) {
-    if constexpr (kQMode != 0) {
-        if (g.tiles_x % 64u != 0u) {  // straddling sets: two-run staged stores (kVarStraddle)
-            hipLaunchKernelGGL((roundtrip_kernel<kRecon, kStats, kQMode, 2, true>), roundtrip_grid(g), dim3(kRtBlock),
-                               0, s, img, coef, recon, sums, g, qp);
-            return hipGetLastError();
-        }
-    }
-    hipLaunchKernelGGL((roundtrip_kernel<kRecon, kStats, kQMode>), roundtrip_grid(g), dim3(kRtBlock), 0, s, img,
-                       coef, recon, sums, g, qp);
-    return hipGetLastError();
-}
-template <int kRecon, bool kStats>
-hipError_t go_q(const uint8_t* img, float* coef, void* recon, RtSums* sums, const TileGrid& g, const QParams& qp,
-                int qmode, hipStream_t s) {
-    switch (qmode) {
-        case 2: return go<kRecon, kStats, 2>(img, coef, recon, sums, g, qp, s);
-        case 1: return go<kRecon, kStats, 1>(img, coef, recon, sums, g, qp, s);
-        default: return go<kRecon, kStats, 0>(img, coef, recon, sums, g, qp, s);
-    }
-}
+// roundtrip_kernel as policy::roundtrip chose it (c: the quotient, and with the
+// verified quotient the two-run staged stores of straddling sets, kVarStraddle)
 template <int kRecon>
 hipError_t go_r(const uint8_t* img, float* coef, void* recon, RtSums* sums, const TileGrid& g, const QParams& qp,
-                int qmode, hipStream_t s) {
-    if (sums) return go_q<kRecon, true>(img, coef, recon, sums, g, qp, qmode, s);
-    return go_q<kRecon, false>(img, coef, recon, sums, g, qp, qmode, s);
+                const policy::Choice& c, hipStream_t s) {
+    return policy::with_quotient<true>(c.var, [&](auto kQ) {
+        constexpr int kQMode = policy::qmode_of(decltype(kQ)::value);
+        return policy::with_bit<kVarStraddle, kQMode != 0>(c.var, [&](auto kS) {
+            constexpr bool kStraddle = decltype(kS)::value != 0u;
+            auto go = [&](auto kStats) {
+                return launch_capped<roundtrip_kernel<kRecon, decltype(kStats)::value, kQMode, 2, kStraddle>>(
+                    dim3(c.grid_x), dim3(c.block), c.cap_wgs, s, img, coef, recon, sums, g, qp);
+            };
+            return sums ? go(std::true_type{}) : go(std::false_type{});
+        });
+    });
 }
 }  // namespace rt_detail
 

@@ -460,42 +460,23 @@ inline dim3 roundtrip_duo_grid(const TileGrid& g, uint32_t block = 256, uint32_t
 }
 
 namespace rt_duo_detail {
-// 256-thread workgroups, 6 waves per SIMD (74 VGPRs, no spills; 7 and 8
-// spill and run slower, tools/kb_rt, profiles/r05/a/).  Whole runs only
-// (tiles_x a multiple of 32, launch_roundtrip checks): the kRun = false kernel
-// (ragged widths, 92 VGPRs) is slower than the tile kernel there (4096 x 4104:
-// 36.9 against 31.9 us with sums, profiles/r05/b/kb_rt_ragged.log).
-// Round 6: at most kDuoRtCapWgs workgroups (16 waves) per CU, by the
-// dynamic-LDS reservation, for the fp32 reconstruction and for every round
-// trip without sums: 8192^2 fp32 reconstruction + sums 100.2-100.3 against
-// 106.6-106.7 us uncapped, without sums 98.9 against 102.4; uint8
-// reconstruction without sums 67.2 against 68.4 (tools/kb_rt group f32cap,
-// profiles/r06/kb_rt_f32cap.log).  The uint8 reconstruction with sums (the C3
-// one pass) gains nothing from it (group rtcap) and stays uncapped.
-constexpr int kDuoRtBlock = 256, kDuoRtWaves = 6;
-constexpr uint32_t kDuoRtCapWgs = 4;
-template <bool kStats, int kQMode, int kRecon>
-hipError_t go(const uint8_t* img, float* coef, void* recon, unsigned long long* spread, const TileGrid& g,
-              const QParams& qp, hipStream_t s) {
-    auto* const kern = roundtrip_duo_kernel<kStats, kQMode, kRecon, true, kDuoRtBlock, kDuoRtWaves>;
-    size_t dyn = 0;
-    if constexpr (kRecon == kRtReconF32 || !kStats) {
-        static const size_t st = static_lds_of(kern);
-        dyn = residency_cap_lds(st, kDuoRtCapWgs);
-    }
-    hipLaunchKernelGGL(kern, roundtrip_duo_grid(g, kDuoRtBlock), dim3(kDuoRtBlock), dyn, s, img, coef, recon,
-                       reinterpret_cast<RtSums*>(spread), g, qp);
-    return hipGetLastError();
-}
+// roundtrip_duo_kernel as policy::roundtrip chose it (c: the quotient, the
+// workgroup size, the cap): whole runs, kDuoRtWaves waves per SIMD.
+constexpr int kDuoRtWaves = 6;
 template <int kRecon>
 hipError_t go_r(const uint8_t* img, float* coef, void* recon, unsigned long long* spread, const TileGrid& g,
-                const QParams& qp, int qmode, hipStream_t s) {
-    if (spread) {
-        return qmode == 2 ? go<true, 2, kRecon>(img, coef, recon, spread, g, qp, s)
-                          : go<true, 1, kRecon>(img, coef, recon, spread, g, qp, s);
-    }
-    return qmode == 2 ? go<false, 2, kRecon>(img, coef, recon, nullptr, g, qp, s)
-                      : go<false, 1, kRecon>(img, coef, recon, nullptr, g, qp, s);
+                const QParams& qp, const policy::Choice& c, hipStream_t s) {
+    auto go = [&](auto kStats, auto kQ) {
+        constexpr int kQMode = policy::qmode_of(decltype(kQ)::value);
+        return launch_capped<roundtrip_duo_kernel<decltype(kStats)::value, kQMode, kRecon, true, policy::kDuoRtBlock,
+                                                  kDuoRtWaves>>(dim3(c.grid_x), dim3(c.block), c.cap_wgs, s, img, coef,
+                                                                recon, reinterpret_cast<RtSums*>(spread), g, qp);
+    };
+    // the verified quotient only (policy::roundtrip): kVarFastDiv with or without kVarJpegQ
+    return policy::with_bit<kVarJpegQ, true>(c.var, [&](auto kJ) {
+        constexpr auto kQ = std::integral_constant<unsigned, kVarFastDiv | decltype(kJ)::value>{};
+        return spread ? go(std::true_type{}, kQ) : go(std::false_type{}, kQ);
+    });
 }
 }  // namespace rt_duo_detail
 

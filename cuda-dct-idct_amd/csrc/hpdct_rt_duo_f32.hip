@@ -6,8 +6,8 @@
 namespace hpdct {
 
 hipError_t launch_rt_duo_f32(const uint8_t* img, float* coef, void* recon, unsigned long long* spread,
-                             const TileGrid& g, const QParams& qp, int fast, hipStream_t s) {
-    return rt_duo_detail::go_r<kRtReconF32>(img, coef, recon, spread, g, qp, fast, s);
+                             const TileGrid& g, const QParams& qp, const policy::Choice& c, hipStream_t s) {
+    return rt_duo_detail::go_r<kRtReconF32>(img, coef, recon, spread, g, qp, c, s);
 }
 
 }  // namespace hpdct

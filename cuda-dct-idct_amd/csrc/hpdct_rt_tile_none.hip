@@ -6,8 +6,8 @@
 namespace hpdct {
 
 hipError_t launch_rt_tile_none(const uint8_t* img, float* coef, void* recon, RtSums* sums, const TileGrid& g,
-                           const QParams& qp, int fast, hipStream_t s) {
-    return rt_detail::go_r<kRtReconNone>(img, coef, recon, sums, g, qp, fast, s);
+                           const QParams& qp, const policy::Choice& c, hipStream_t s) {
+    return rt_detail::go_r<kRtReconNone>(img, coef, recon, sums, g, qp, c, s);
 }
 
 }  // namespace hpdct

@@ -501,8 +501,8 @@ def test_video_widths_large_frames(hp, oracle, dev, h, w):
 @pytest.mark.parametrize("qtab", ["jpeg", "fractional"])
 def test_capped_packed_forward_large_frames(hp, oracle, dev, h, w, qtab):
     """u8 -> fp32 frames of more than 32 sets per CU take the one-wave,
-    residency-capped (7 per CU), packed-fp32 kernel (hpdct_launch.hpp
-    fdct_tile_go): 4104 x 8200 (32.1 sets per CU), 6000 x 8008 (45.8); frames
+    residency-capped (7 per CU), packed-fp32 kernel (hpdct_policy.hpp
+    forward): 4104 x 8200 (32.1 sets per CU), 6000 x 8008 (45.8); frames
     of up to 32 take the uncapped 1024-thread kernel: 2048 x 16384 (the C4
     8-way slab, exactly 32).  Ragged widths (tiles_x not a multiple of 64:
     sets straddle tile rows) and a ragged last set; the JPEG table (per-position
@@ -525,7 +525,7 @@ def test_capped_packed_forward_large_frames(hp, oracle, dev, h, w, qtab):
 def test_capped_duo_writebacks_large_frame(hp, oracle, dev):
     """fp32 frames of >= 64 duo waves per CU (here 4096 x 8200: 524,800 tiles,
     16,400 waves of 32 tiles on 256 CUs) take the one-wave, residency-capped
-    duo kernels (hpdct_launch.hpp DuoShape): the rows-first forward with the
+    duo kernels (hpdct_policy.hpp duo_f32): the rows-first forward with the
     X-128 write-back, the rows-first inverse with the q*Q write-back and the
     reference-order inverse with the q*Q write-back; since round 6 also the
     reference-order forward (dct_all_blocks_cuda's kernel, checked quotient)

@@ -38,9 +38,8 @@ void one_shot(const int8_t* in, float* out, uint64_t n, hipStream_t s) {
 // one-wave workgroups, at most kCap resident per CU (dynamic-LDS reservation, as the headline)
 template <int kU, uint32_t kCap>
 void capped(const int8_t* in, float* out, uint64_t n, hipStream_t s) {
-    auto* k = decode_i8_f32_kernel<64, kU, false>;
-    static const size_t dyn = residency_cap_lds(static_lds_of(k), kCap);
-    hipLaunchKernelGGL(k, dim3((uint32_t)decode_blocks<64, kU>(n, 0)), dim3(64), dyn, s, in, out, n);
+    (void)launch_capped<decode_i8_f32_kernel<64, kU, false>>(dim3((uint32_t)decode_blocks<64, kU>(n, 0)), dim3(64), kCap, s,
+                                                             in, out, n);
 }
 // persistent: kWavesPerCU waves per CU walk the plane
 template <int kB, int kU, uint32_t kWavesPerCU>

@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "hpdct_fill_hash.hpp"
 #include "hpdct_launch.hpp"
 #include "kbench_rtduo_pk.hpp"
 #include "kbench_rtfold.hpp"
@@ -26,15 +27,12 @@ int hpdct::mapping_mode() { return 0; }
 // the library's duo-forward launcher (hpdct_rt_duo.hip), which launch_fdct_impl calls
 template <int kQ>
 static hipError_t duo_fwd_lib(const uint8_t* img, float* coef, const TileGrid& g, const QParams& qp, hipStream_t s) {
-    auto* const kern = fdct_duo_u8_kernel<kQ>;
-    static const size_t st = static_lds_of(kern);
-    hipLaunchKernelGGL(kern, roundtrip_duo_grid(g, kDuoFwdBlock), dim3(kDuoFwdBlock),
-                       residency_cap_lds(st, kDuoFwdCapWgs), s, img, coef, g, qp);
-    return hipGetLastError();
+    return launch_capped<fdct_duo_u8_kernel<kQ>>(roundtrip_duo_grid(g, policy::kDuoFwdBlock),
+                                                 dim3(policy::kDuoFwdBlock), policy::kDuoFwdCapWgs, s, img, coef, g, qp);
 }
 hipError_t hpdct::launch_fdct_duo_u8(const uint8_t* img, float* coef, const TileGrid& g, const QParams& qp,
-                                     int qmode, hipStream_t s) {
-    return qmode == 2 ? duo_fwd_lib<2>(img, coef, g, qp, s) : duo_fwd_lib<1>(img, coef, g, qp, s);
+                                     const policy::Choice& c, hipStream_t s) {
+    return (c.var & kVarJpegQ) != 0u ? duo_fwd_lib<2>(img, coef, g, qp, s) : duo_fwd_lib<1>(img, coef, g, qp, s);
 }
 
 #define CK(x)                                                                        \
@@ -153,10 +151,9 @@ void duo_ring(const uint8_t* img, float* coef, uint8_t* recon, const Ctx& c, hip
 // kernel's registers allow 6 (24 waves per CU)
 template <bool kStats, int kWgs>
 void duo_cap(const uint8_t* img, float* coef, uint8_t* recon, const Ctx& c, hipStream_t s) {
-    auto kern = roundtrip_duo_kernel<kStats, 2, kRtReconU8, true, 256, 6>;
-    static const size_t dyn = residency_cap_lds(static_lds_of(kern), kWgs);
+    constexpr auto kern = roundtrip_duo_kernel<kStats, 2, kRtReconU8, true, 256, 6>;
     RtSums* const sp = reinterpret_cast<RtSums*>(kStats ? g_spread : nullptr);
-    hipLaunchKernelGGL(kern, roundtrip_duo_grid(c.g, 256), dim3(256), dyn, s, img, coef, recon, sp, c.g, c.qp);
+    (void)launch_capped<kern>(roundtrip_duo_grid(c.g, 256), dim3(256), kWgs, s, img, coef, recon, sp, c.g, c.qp);
     if (kStats) hipLaunchKernelGGL(rt_spread_finish_kernel<>, dim3(1), dim3(64), 0, s, c.sums, g_spread, 0);
 }
 
@@ -174,9 +171,8 @@ void headline_product(const uint8_t* img, float* coef, uint8_t*, const Ctx& c, h
 // workgroup size; kWgs: resident workgroups per CU (0: no cap)
 template <int kB, int kWgs>
 void duo_fwd(const uint8_t* img, float* coef, uint8_t*, const Ctx& c, hipStream_t s) {
-    auto kern = roundtrip_duo_kernel<false, 2, kRtReconNone, true, kB, 6>;
-    static const size_t dyn = residency_cap_lds(static_lds_of(kern), kWgs);
-    hipLaunchKernelGGL(kern, roundtrip_duo_grid(c.g, kB), dim3(kB), dyn, s, img, coef, nullptr, nullptr, c.g, c.qp);
+    constexpr auto kern = roundtrip_duo_kernel<false, 2, kRtReconNone, true, kB, 6>;
+    (void)launch_capped<kern>(roundtrip_duo_grid(c.g, kB), dim3(kB), kWgs, s, img, coef, nullptr, nullptr, c.g, c.qp);
 }
 // round 6: the int8 wire format on the duo forward (the plane passed as
 // float* is written as px int8 bytes)
@@ -186,17 +182,15 @@ void headline_i8_product(const uint8_t* img, float* coef, uint8_t*, const Ctx& c
 }
 template <int kWgs>
 void duo_i8(const uint8_t* img, float* coef, uint8_t*, const Ctx& c, hipStream_t s) {
-    auto kern = fdct_duo_u8_kernel<2, int8_t>;
-    static const size_t dyn = residency_cap_lds(static_lds_of(kern), kWgs);
-    hipLaunchKernelGGL(kern, roundtrip_duo_grid(c.g, 256), dim3(256), dyn, s, img, reinterpret_cast<int8_t*>(coef),
+    constexpr auto kern = fdct_duo_u8_kernel<2, int8_t>;
+    (void)launch_capped<kern>(roundtrip_duo_grid(c.g, 256), dim3(256), kWgs, s, img, reinterpret_cast<int8_t*>(coef),
                        c.g, c.qp);
 }
 // kSets runs of 32 tiles per wave (a grid apart), forward only
 template <int kSets, int kWgs>
 void duo_fwd_s(const uint8_t* img, float* coef, uint8_t*, const Ctx& c, hipStream_t s) {
-    auto kern = roundtrip_duo_kernel<false, 2, kRtReconNone, true, 256, 6, kSets>;
-    static const size_t dyn = residency_cap_lds(static_lds_of(kern), kWgs);
-    hipLaunchKernelGGL(kern, roundtrip_duo_grid(c.g, 256, kSets), dim3(256), dyn, s, img, coef, nullptr, nullptr,
+    constexpr auto kern = roundtrip_duo_kernel<false, 2, kRtReconNone, true, 256, 6, kSets>;
+    (void)launch_capped<kern>(roundtrip_duo_grid(c.g, 256, kSets), dim3(256), kWgs, s, img, coef, nullptr, nullptr,
                        c.g, c.qp);
 }
 // the fp32-reconstruction round trip (+ sums + fold), capped; the recon plane
@@ -204,9 +198,8 @@ void duo_fwd_s(const uint8_t* img, float* coef, uint8_t*, const Ctx& c, hipStrea
 // reconstruction check against the uint8 product is moot: run with KB_CONTINUE)
 template <bool kStats, int kWgs>
 void duo_f32rt(const uint8_t* img, float* coef, uint8_t* recon, const Ctx& c, hipStream_t s) {
-    auto kern = roundtrip_duo_kernel<kStats, 2, kRtReconF32, true, 256, 6>;
-    static const size_t dyn = residency_cap_lds(static_lds_of(kern), kWgs);
-    hipLaunchKernelGGL(kern, roundtrip_duo_grid(c.g, 256), dim3(256), dyn, s, img, coef, static_cast<void*>(recon),
+    constexpr auto kern = roundtrip_duo_kernel<kStats, 2, kRtReconF32, true, 256, 6>;
+    (void)launch_capped<kern>(roundtrip_duo_grid(c.g, 256), dim3(256), kWgs, s, img, coef, static_cast<void*>(recon),
                        reinterpret_cast<RtSums*>(kStats ? g_spread : nullptr), c.g, c.qp);
     if (kStats) hipLaunchKernelGGL(rt_spread_finish_kernel<>, dim3(1), dim3(64), 0, s, c.sums, g_spread, 0);
 }

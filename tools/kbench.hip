@@ -142,7 +142,7 @@ struct Variant {
 
 template <unsigned kVar>
 void launch_var(const uint8_t* in, float* out, const TileGrid& g, const QParams& qp, uint32_t cus, hipStream_t s) {
-    const dim3 grid = grid_for(g, (kVar & ab::kVarPersist) != 0, cus, kBlock<kVar>);
+    const dim3 grid = ab::grid_for(g, (kVar & ab::kVarPersist) != 0, cus, kBlock<kVar>);
     hipLaunchKernelGGL((ab::fdct_kernel<uint8_t, float, true, true, false, kVar>), grid, dim3(kBlock<kVar>), 0, s, in,
                        out, nullptr, g, nullptr, qp, 128.0f);
 }
@@ -161,7 +161,7 @@ void launch_var_occ(const uint8_t* in, float* out, const TileGrid& g, const QPar
 template <typename TI, typename TO, unsigned kVar>
 void launch_fwd_any(const uint8_t* in, float* out, const TileGrid& g, const QParams& qp, uint32_t cus,
                     hipStream_t s) {
-    hipLaunchKernelGGL((ab::fdct_kernel<TI, TO, true, true, false, kVar>), grid_for(g, false, cus, kBlock<kVar>),
+    hipLaunchKernelGGL((ab::fdct_kernel<TI, TO, true, true, false, kVar>), grid_for(g, kBlock<kVar>),
                        dim3(kBlock<kVar>),
                        0, s, reinterpret_cast<const TI*>(in), reinterpret_cast<TO*>(out), nullptr, g, nullptr, qp,
                        128.0f);
@@ -169,7 +169,7 @@ void launch_fwd_any(const uint8_t* in, float* out, const TileGrid& g, const QPar
 template <typename TI, typename TO, unsigned kVar>
 void launch_inv_any(const uint8_t* in, float* out, const TileGrid& g, const QParams& qp, uint32_t cus,
                     hipStream_t s) {
-    hipLaunchKernelGGL((ab::idct_kernel<TI, TO, true, true, kVar>), grid_for(g, false, cus, kBlock<kVar>),
+    hipLaunchKernelGGL((ab::idct_kernel<TI, TO, true, true, kVar>), grid_for(g, kBlock<kVar>),
                        dim3(kBlock<kVar>), 0, s,
                        reinterpret_cast<const TI*>(in), reinterpret_cast<TO*>(out), nullptr, g, nullptr, qp.q, 128.0f);
 }
@@ -193,7 +193,7 @@ float* g_wb = nullptr;
 template <unsigned kVar>
 void launch_fwd_compat_tile(const uint8_t* in, float* out, const TileGrid& g, const QParams& qp, uint32_t,
                             hipStream_t s) {
-    hipLaunchKernelGGL((ab::fdct_kernel<float, float, true, false, true, kVar>), grid_for(g, false, 0, kBlock<kVar>),
+    hipLaunchKernelGGL((ab::fdct_kernel<float, float, true, false, true, kVar>), grid_for(g, kBlock<kVar>),
                        dim3(kBlock<kVar>), 0, s, reinterpret_cast<const float*>(in), out, g_wb, g, g_T, qp, 128.0f);
 }
 template <unsigned kVar>
@@ -213,7 +213,7 @@ template <unsigned kVar>
 void launch_cublas_fwd_tile(const uint8_t* in, float* out, const TileGrid& g, const QParams& qp, uint32_t,
                             hipStream_t s) {
     hipLaunchKernelGGL((ab::fdct_kernel<float, float, true, false, true, kVar | kVarRowFirst>),
-                       grid_for(g, false, 0, kBlock<kVar>), dim3(kBlock<kVar>), 0, s,
+                       grid_for(g, kBlock<kVar>), dim3(kBlock<kVar>), 0, s,
                        reinterpret_cast<const float*>(in), out, g_wb, g, g_T, qp, 128.0f);
 }
 template <unsigned kVar>
@@ -226,7 +226,7 @@ template <unsigned kVar>
 void launch_cublas_inv_tile(const uint8_t* in, float* out, const TileGrid& g, const QParams& qp, uint32_t,
                             hipStream_t s) {
     hipLaunchKernelGGL((ab::idct_kernel<float, float, true, false, kVar | kVarRowFirst | kVarWbDequant>),
-                       grid_for(g, false, 0, kBlock<kVar>), dim3(kBlock<kVar>), 0, s,
+                       grid_for(g, kBlock<kVar>), dim3(kBlock<kVar>), 0, s,
                        reinterpret_cast<const float*>(in), out, g_wb, g, g_T, qp.q, 128.0f);
 }
 template <unsigned kVar>
@@ -254,7 +254,7 @@ void launch_inv_duo(const uint8_t* in, float* out, const TileGrid& g, const QPar
 template <typename TI, typename TO, unsigned kVar>
 void launch_fwd_pers(const uint8_t* in, float* out, const TileGrid& g, const QParams& qp, uint32_t cus,
                      hipStream_t s) {
-    hipLaunchKernelGGL((ab::fdct_kernel<TI, TO, true, true, false, kVar>), grid_for(g, true, cus, kBlock<kVar>),
+    hipLaunchKernelGGL((ab::fdct_kernel<TI, TO, true, true, false, kVar>), ab::grid_for(g, true, cus, kBlock<kVar>),
                        dim3(kBlock<kVar>), 0, s, reinterpret_cast<const TI*>(in), reinterpret_cast<TO*>(out), nullptr,
                        g, nullptr, qp, 128.0f);
 }
@@ -358,7 +358,7 @@ int main(int argc, char** argv) {
         CK(hipMemcpy(inf[s], hf.data(), px * 4, hipMemcpyHostToDevice));
     }
     constexpr unsigned F = kVarFastDiv, X = ab::kVarXorCvt, L = kVarLdsStore, N = kVarNT, P = ab::kVarPersist;
-    constexpr unsigned B = L | N | F, R = ab::kVarRowMajor, S = ab::kVarLdsSwz, W512 = 2u << 12, W1024 = 3u << 12;
+    constexpr unsigned B = L | N | F, R = ab::kVarRowMajor, S = ab::kVarLdsSwz, W512 = with_block<512>(0u), W1024 = with_block<1024>(0u);
     constexpr unsigned LL = ab::kVarLdsLoad;
     constexpr unsigned NL = ab::kVarNTLoad, IP = kVarI8Pack;
     constexpr unsigned PK = ab::kVarPacked, OR = kOctRestage;

@@ -66,7 +66,7 @@ struct Variant {
 // ---- inverse fp32 -> u8 ----------------------------------------------------
 template <unsigned kVar>
 void inv_tile(const void* in, void* out, const Ctx& c, hipStream_t s) {
-    hipLaunchKernelGGL((ab::idct_kernel<float, uint8_t, true, true, kVar>), grid_for(c.g, false, c.cus, kBlock<kVar>),
+    hipLaunchKernelGGL((ab::idct_kernel<float, uint8_t, true, true, kVar>), grid_for(c.g, kBlock<kVar>),
                        dim3(kBlock<kVar>), 0, s, static_cast<const float*>(in), static_cast<uint8_t*>(out), nullptr,
                        c.g, nullptr, c.qp.q, 128.0f);
 }
@@ -87,7 +87,7 @@ void inv_duo(const void* in, void* out, const Ctx& c, hipStream_t s) {
 template <unsigned kVar, uint32_t kLdsBytes = 0>
 void i8_fwd(const void* in, void* out, const Ctx& c, hipStream_t s) {
     hipLaunchKernelGGL((ab::fdct_kernel<uint8_t, int8_t, true, true, false, kVar>),
-                       grid_for(c.g, false, c.cus, kBlock<kVar>), dim3(kBlock<kVar>), kLdsBytes, s,
+                       grid_for(c.g, kBlock<kVar>), dim3(kBlock<kVar>), kLdsBytes, s,
                        static_cast<const uint8_t*>(in), static_cast<int8_t*>(out), nullptr, c.g, nullptr, c.qp,
                        128.0f);
 }
@@ -105,7 +105,7 @@ void i8_fwd_two(const void* in, void* out, const Ctx& c, hipStream_t s) {
 template <unsigned kVar>
 void i8_fwd_persist(const void* in, void* out, const Ctx& c, hipStream_t s) {
     hipLaunchKernelGGL((ab::fdct_kernel<uint8_t, int8_t, true, true, false, kVar | ab::kVarPersist2>),
-                       grid_for(c.g, true, c.cus, kBlock<kVar>), dim3(kBlock<kVar>), 0, s,
+                       ab::grid_for(c.g, true, c.cus, kBlock<kVar>), dim3(kBlock<kVar>), 0, s,
                        static_cast<const uint8_t*>(in), static_cast<int8_t*>(out), nullptr, c.g, nullptr, c.qp,
                        128.0f);
 }
@@ -114,7 +114,7 @@ void i8_fwd_persist(const void* in, void* out, const Ctx& c, hipStream_t s) {
 template <unsigned kVar, uint32_t kLdsBytes = 0>
 void f32_fwd(const void* in, void* out, const Ctx& c, hipStream_t s) {
     hipLaunchKernelGGL((ab::fdct_kernel<uint8_t, float, true, true, false, kVar>),
-                       grid_for(c.g, false, c.cus, kBlock<kVar>), dim3(kBlock<kVar>), kLdsBytes, s,
+                       grid_for(c.g, kBlock<kVar>), dim3(kBlock<kVar>), kLdsBytes, s,
                        static_cast<const uint8_t*>(in), static_cast<float*>(out), nullptr, c.g, nullptr, c.qp,
                        128.0f);
 }
@@ -131,7 +131,7 @@ void f32_fwd_two(const void* in, void* out, const Ctx& c, hipStream_t s) {
 template <unsigned kVar>
 void f32_fwd_persist(const void* in, void* out, const Ctx& c, hipStream_t s) {
     hipLaunchKernelGGL((ab::fdct_kernel<uint8_t, float, true, true, false, kVar | ab::kVarPersist2>),
-                       grid_for(c.g, true, c.cus, kBlock<kVar>), dim3(kBlock<kVar>), 0, s,
+                       ab::grid_for(c.g, true, c.cus, kBlock<kVar>), dim3(kBlock<kVar>), 0, s,
                        static_cast<const uint8_t*>(in), static_cast<float*>(out), nullptr, c.g, nullptr, c.qp, 128.0f);
 }
 
@@ -139,13 +139,13 @@ void f32_fwd_persist(const void* in, void* out, const Ctx& c, hipStream_t s) {
 template <unsigned kVar>
 void prod_f32_fwd(const void* in, void* out, const Ctx& c, hipStream_t s) {
     hipLaunchKernelGGL((hpdct::fdct_kernel<uint8_t, float, true, true, false, kVar>),
-                       grid_for(c.g, false, c.cus, kBlock<kVar>), dim3(kBlock<kVar>), 0, s,
+                       grid_for(c.g, kBlock<kVar>), dim3(kBlock<kVar>), 0, s,
                        static_cast<const uint8_t*>(in), static_cast<float*>(out), nullptr, c.g, nullptr, c.qp, 128.0f);
 }
 template <unsigned kVar>
 void prod_i8_fwd(const void* in, void* out, const Ctx& c, hipStream_t s) {
     hipLaunchKernelGGL((hpdct::fdct_kernel<uint8_t, int8_t, true, true, false, kVar>),
-                       grid_for(c.g, false, c.cus, kBlock<kVar>), dim3(kBlock<kVar>), 0, s,
+                       grid_for(c.g, kBlock<kVar>), dim3(kBlock<kVar>), 0, s,
                        static_cast<const uint8_t*>(in), static_cast<int8_t*>(out), nullptr, c.g, nullptr, c.qp, 128.0f);
 }
 
@@ -186,7 +186,7 @@ int set_of(const void* in) {
 void rt_two_kernels(const void* in, void* out, const Ctx& c, hipStream_t s) {
     float* cf = g_coef2[set_of(in)];
     hipLaunchKernelGGL((ab::fdct_kernel<uint8_t, float, true, true, false, kProdVar<uint8_t, float> | kVarFastDiv>),
-                       grid_for(c.g, false, c.cus, kBlock<kProdVar<uint8_t, float>>),
+                       grid_for(c.g, kBlock<kProdVar<uint8_t, float>>),
                        dim3(kBlock<kProdVar<uint8_t, float>>), 0, s, static_cast<const uint8_t*>(in), cf, nullptr, c.g,
                        nullptr, c.qp, 128.0f);
     (void)launch_idct_impl<float, uint8_t, true, true>(cf, static_cast<uint8_t*>(out), nullptr, c.g, nullptr, c.qp.q, 128.0f,
@@ -195,9 +195,11 @@ void rt_two_kernels(const void* in, void* out, const Ctx& c, hipStream_t s) {
 template <int kRecon, bool kStats, bool kFast>
 void rt_fused(const void* in, void* out, const Ctx& c, hipStream_t s) {
     if (kStats) (void)hipMemsetAsync(g_sums, 0, sizeof(RtSums), s);
+    policy::RtCall rc;  // the tile-per-lane kernel
+    rc.g = c.g, rc.qmode = kFast, rc.mapping = HPDCT_MAPPING_TILE;
     (void)rt_detail::go_r<kRecon>(static_cast<const uint8_t*>(in), g_coef2[set_of(in)],
                                   kRecon == kRtReconNone ? nullptr : out, kStats ? g_sums : nullptr, c.g, c.qp,
-                                  kFast, s);
+                                  policy::roundtrip(rc), s);
 }
 
 template <int kRaw, bool kMemset = true>
@@ -256,7 +258,7 @@ int main(int argc, char** argv) {
         for (size_t i = 0; i < px; ++i) hs[i] = h[(i * 7919u + 13u * s) % px];
         CK(hipMemcpy(img[s], hs.data(), px, hipMemcpyHostToDevice));
         hipLaunchKernelGGL((ab::fdct_kernel<uint8_t, float, true, true, false, kProdVar<uint8_t, float>>),
-                           grid_for(c.g, false, c.cus, kBlock<kProdVar<uint8_t, float>>),
+                           grid_for(c.g, kBlock<kProdVar<uint8_t, float>>),
                            dim3(kBlock<kProdVar<uint8_t, float>>), 0, 0, img[s], coef[s], nullptr, c.g, nullptr, c.qp,
                            128.0f);
     }
@@ -266,7 +268,7 @@ int main(int argc, char** argv) {
     for (int s = 0; s < nsets; ++s) dalloc(&g_coef2[s], px * 4);
     CK(hipMalloc(&g_sums, sizeof(RtSums)));
 
-    constexpr unsigned N = kVarNT, W512 = 2u << 12, W1024 = 3u << 12, LL = ab::kVarLdsLoad, OR = kOctRestage;
+    constexpr unsigned N = kVarNT, W512 = with_block<512>(0u), W1024 = with_block<1024>(0u), LL = ab::kVarLdsLoad, OR = kOctRestage;
     constexpr unsigned F = kVarFastDiv, IP = kVarI8Pack;
     constexpr unsigned I8 = F | N | W512 | IP;  // the product's int8 forward
     std::vector<Variant> vars = {
@@ -304,15 +306,15 @@ int main(int argc, char** argv) {
         {"wide", "fwd u8->f32 tile (product)", f32_fwd<kProdVar<uint8_t, float> | F>, true},
         {"wide", "fwd u8->f32 tile panel 4096 px", f32_fwd<kProdVar<uint8_t, float> | F | ab::kVarPanel>, true},
         {"wide", "fwd u8->f32 tile nt loads", f32_fwd<kProdVar<uint8_t, float> | F | ab::kVarNTLoad>, true},
-        {"wide", "fwd u8->f32 tile b256", f32_fwd<(kProdVar<uint8_t, float> & ~(3u << 12)) | F>, true},
-        {"wide", "fwd u8->f32 tile b1024", f32_fwd<(kProdVar<uint8_t, float> & ~(3u << 12)) | W1024 | F>, true},
+        {"wide", "fwd u8->f32 tile b256", f32_fwd<with_block<256>(kProdVar<uint8_t, float>) | F>, true},
+        {"wide", "fwd u8->f32 tile b1024", f32_fwd<with_block<1024>(kProdVar<uint8_t, float>) | F>, true},
         {"wide", "fwd u8->f32 tile lds 1 wg/cu (2 w/simd)", f32_fwd<kProdVar<uint8_t, float> | F, 100 * 1024>, true},
         {"wide", "fwd u8->f32 tile lds 2 wg/cu (4 w/simd)", f32_fwd<kProdVar<uint8_t, float> | F, 60 * 1024>, true},
         {"wide", "fwd u8->f32 tile lds 3 wg/cu (6 w/simd)", f32_fwd<kProdVar<uint8_t, float> | F, 36 * 1024>, true},
-        {"wide", "fwd u8->f32 tile b256 lds 2 wg/cu (2 w/simd)", f32_fwd<(kProdVar<uint8_t, float> & ~(3u << 12)) | F, 60 * 1024>, true},
-        {"wide", "fwd u8->f32 tile b256 lds 3 wg/cu (3 w/simd)", f32_fwd<(kProdVar<uint8_t, float> & ~(3u << 12)) | F, 40 * 1024>, true},
+        {"wide", "fwd u8->f32 tile b256 lds 2 wg/cu (2 w/simd)", f32_fwd<with_block<256>(kProdVar<uint8_t, float>) | F, 60 * 1024>, true},
+        {"wide", "fwd u8->f32 tile b256 lds 3 wg/cu (3 w/simd)", f32_fwd<with_block<256>(kProdVar<uint8_t, float>) | F, 40 * 1024>, true},
         {"wide", "fwd u8->f32 tile two sets/wave", f32_fwd_two<kProdVar<uint8_t, float> | F>, true},
-        {"wide", "fwd u8->f32 tile two sets/wave b256", f32_fwd_two<(kProdVar<uint8_t, float> & ~(3u << 12)) | F>, true},
+        {"wide", "fwd u8->f32 tile two sets/wave b256", f32_fwd_two<with_block<256>(kProdVar<uint8_t, float>) | F>, true},
         {"wide", "fwd u8->f32 tile persistent+prefetch", f32_fwd_persist<kProdVar<uint8_t, float> | F>, true},
         {"wide", "fwd u8->f32 tile (product) again", f32_fwd<kProdVar<uint8_t, float> | F>, true},
         {"tlb", "fwd u8->f32 library kernel", prod_f32_fwd<kProdVar<uint8_t, float> | F>, true},
@@ -325,7 +327,7 @@ int main(int argc, char** argv) {
         // linear 4 KiB input reads staged through LDS (kbench_linread.hpp) against the library kernel
         {"lin", "fwd u8->f32 library (b512)", prod_f32_fwd<kProdVar<uint8_t, float> | F>, true},
         {"lin", "fwd u8->f32 linear reads via LDS (b1024)", lin_f32_fwd, true},
-        {"lin", "fwd u8->f32 library b1024", prod_f32_fwd<(kProdVar<uint8_t, float> & ~(3u << 12)) | W1024 | F>, true},
+        {"lin", "fwd u8->f32 library b1024", prod_f32_fwd<with_block<1024>(kProdVar<uint8_t, float>) | F>, true},
         {"lin", "fwd u8->f32 library (b512) again", prod_f32_fwd<kProdVar<uint8_t, float> | F>, true},
         {"lin", "fwd u8->f32 linear reads via LDS again", lin_f32_fwd, true},
         // linear reads through an LDS-DMA double buffer (kbench_dma.hpp): waves per workgroup x workgroups per CU

@@ -16,6 +16,7 @@
 #include <string>
 #include <vector>
 
+#include "hpdct_fill_hash.hpp"
 #include "hpdct_launch.hpp"
 #include "kbench_dma.hpp"
 #include "kbench_band.hpp"
@@ -52,7 +53,7 @@ struct Variant {
 template <unsigned kVar>
 void prod_f32_fwd(const void* in, void* out, const Ctx& c, hipStream_t s) {
     hipLaunchKernelGGL((hpdct::fdct_kernel<uint8_t, float, true, true, false, kVar>),
-                       grid_for(c.g, false, c.cus, kBlock<kVar>), dim3(kBlock<kVar>), 0, s,
+                       grid_for(c.g, kBlock<kVar>), dim3(kBlock<kVar>), 0, s,
                        static_cast<const uint8_t*>(in), static_cast<float*>(out), nullptr, c.g, nullptr, c.qp, 128.0f);
 }
 
@@ -75,7 +76,7 @@ void band_fwd(const void* in, void* out, const Ctx& c, hipStream_t s) {
 template <unsigned kVar>
 void prod_i8_fwd(const void* in, void* out, const Ctx& c, hipStream_t s) {
     hipLaunchKernelGGL((hpdct::fdct_kernel<uint8_t, int8_t, true, true, false, kVar>),
-                       grid_for(c.g, false, c.cus, kBlock<kVar>), dim3(kBlock<kVar>), 0, s,
+                       grid_for(c.g, kBlock<kVar>), dim3(kBlock<kVar>), 0, s,
                        static_cast<const uint8_t*>(in), static_cast<int8_t*>(out), nullptr, c.g, nullptr, c.qp, 128.0f);
 }
 
@@ -92,7 +93,7 @@ void oct_f32_fwd(const void* in, void* out, const Ctx& c, hipStream_t s) {
 template <typename TOut, unsigned kVar>
 void ab_fwd(const void* in, void* out, const Ctx& c, hipStream_t s) {
     hipLaunchKernelGGL((hpdct::ab::fdct_kernel<uint8_t, TOut, true, true, false, kVar>),
-                       grid_for(c.g, false, c.cus, ab::kBlock<kVar>), dim3(ab::kBlock<kVar>), 0, s,
+                       grid_for(c.g, ab::kBlock<kVar>), dim3(ab::kBlock<kVar>), 0, s,
                        static_cast<const uint8_t*>(in), static_cast<TOut*>(out), nullptr, c.g, nullptr, c.qp, 128.0f);
 }
 
@@ -265,7 +266,7 @@ void ab_fwd_cap(const void* in, void* out, const Ctx& c, hipStream_t s) {
     constexpr uint32_t kB = ab::kBlock<kVar>;
     auto* k = hpdct::ab::fdct_kernel<uint8_t, TOut, true, true, false, kVar>;
     static const size_t dyn = cap_for(k, kWg);
-    hipLaunchKernelGGL(k, grid_for(c.g, false, c.cus, kB), dim3(kB), dyn, s, static_cast<const uint8_t*>(in),
+    hipLaunchKernelGGL(k, grid_for(c.g, kB), dim3(kB), dyn, s, static_cast<const uint8_t*>(in),
                        static_cast<TOut*>(out), nullptr, c.g, nullptr, c.qp, 128.0f);
 }
 // the library's headline kernel itself, capped
@@ -273,7 +274,7 @@ template <unsigned kVar, uint32_t kWg>
 void prod_f32_fwd_cap(const void* in, void* out, const Ctx& c, hipStream_t s) {
     auto* k = hpdct::fdct_kernel<uint8_t, float, true, true, false, kVar>;
     static const size_t dyn = cap_for(k, kWg);
-    hipLaunchKernelGGL(k, grid_for(c.g, false, c.cus, kBlock<kVar>), dim3(kBlock<kVar>), dyn, s,
+    hipLaunchKernelGGL(k, grid_for(c.g, kBlock<kVar>), dim3(kBlock<kVar>), dyn, s,
                        static_cast<const uint8_t*>(in), static_cast<float*>(out), nullptr, c.g, nullptr, c.qp, 128.0f);
 }
 // the library's int8 forward kernel, capped at kWg workgroups per CU (0: uncapped)
@@ -281,7 +282,7 @@ template <unsigned kVar, uint32_t kWg>
 void prod_i8_fwd_cap(const void* in, void* out, const Ctx& c, hipStream_t s) {
     auto* k = hpdct::fdct_kernel<uint8_t, int8_t, true, true, false, kVar>;
     static const size_t dyn = kWg ? cap_for(k, kWg) : 0;
-    hipLaunchKernelGGL(k, grid_for(c.g, false, c.cus, kBlock<kVar>), dim3(kBlock<kVar>), dyn, s,
+    hipLaunchKernelGGL(k, grid_for(c.g, kBlock<kVar>), dim3(kBlock<kVar>), dyn, s,
                        static_cast<const uint8_t*>(in), static_cast<int8_t*>(out), nullptr, c.g, nullptr, c.qp, 128.0f);
 }
 // C3 round trip with a quotient mode (1: verified 3-op, 2: + JPEG per-position forms)
@@ -405,7 +406,9 @@ int main(int argc, char** argv) {
     constexpr unsigned P = kProdVar<uint8_t, float> | F;
     constexpr unsigned I8 = kProdVar<uint8_t, int8_t> | F;
     // the headline's capped variant (one-wave workgroups, packed transform)
-    constexpr unsigned PK1 = (P & ~(3u << 12)) | kOneWaveWg | kVarPacked;
+    constexpr unsigned PK1 = with_block<64>(P) | kVarPacked;
+    // the product's capped headline kernel before the hoisted run test (groups lim / hoist / nolds)
+    constexpr unsigned kLimVar = with_block<64>(kVarFastDiv | kVarJpegQ | kVarLdsStore | kVarNT | kVarPacked);
     std::vector<Variant> vars = {
         {"fwd", "fwd u8->f32 library (b512)", prod_f32_fwd<P>, 5, 4, true},
         {"fwd", "fwd u8->f32 dma 8w x 2/cu", dma_f32_fwd<8, 2>, 5, 4, true},
@@ -416,27 +419,27 @@ int main(int argc, char** argv) {
         {"fwd", "fwd u8->f32 library (b512) again", prod_f32_fwd<P>, 5, 4, true},
         {"fwd", "fwd u8->f32 dma 8w x 2/cu again", dma_f32_fwd<8, 2>, 5, 4, true},
         {"band", "fwd u8->f32 library (b512)", prod_f32_fwd<P>, 5, 4, true},
-        {"band", "fwd u8->f32 band 4 w/cu", band_fwd<float, (P & ~(3u << 12)), 4>, 5, 4, true},
-        {"band", "fwd u8->f32 band 8 w/cu b256", band_fwd<float, (P & ~(3u << 12)), 8>, 5, 4, true},
+        {"band", "fwd u8->f32 band 4 w/cu", band_fwd<float, with_block<256>(P), 4>, 5, 4, true},
+        {"band", "fwd u8->f32 band 8 w/cu b256", band_fwd<float, with_block<256>(P), 8>, 5, 4, true},
         {"band", "fwd u8->f32 band 8 w/cu b512", band_fwd<float, P, 8>, 5, 4, true},
         {"band", "fwd u8->f32 band 16 w/cu b512", band_fwd<float, P, 16>, 5, 4, true},
         {"band", "fwd u8->f32 library (b512) again", prod_f32_fwd<P>, 5, 4, true},
-        {"band", "fwd u8->f32 band 4 w/cu again", band_fwd<float, (P & ~(3u << 12)), 4>, 5, 4, true},
+        {"band", "fwd u8->f32 band 4 w/cu again", band_fwd<float, with_block<256>(P), 4>, 5, 4, true},
         {"bandi8", "fwd u8->i8 library (b512)", prod_i8_fwd<I8>, 2, 1, true},
-        {"bandi8", "fwd u8->i8 band 4 w/cu", band_fwd<int8_t, (I8 & ~(3u << 12)), 4>, 2, 1, true},
-        {"bandi8", "fwd u8->i8 band 8 w/cu b256", band_fwd<int8_t, (I8 & ~(3u << 12)), 8>, 2, 1, true},
+        {"bandi8", "fwd u8->i8 band 4 w/cu", band_fwd<int8_t, with_block<256>(I8), 4>, 2, 1, true},
+        {"bandi8", "fwd u8->i8 band 8 w/cu b256", band_fwd<int8_t, with_block<256>(I8), 8>, 2, 1, true},
         {"bandi8", "fwd u8->i8 band 16 w/cu b512", band_fwd<int8_t, I8, 16>, 2, 1, true},
         {"bandi8", "fwd u8->i8 library (b512) again", prod_i8_fwd<I8>, 2, 1, true},
         {"bandpk", "fwd u8->f32 library (b512)", prod_f32_fwd<P>, 5, 4, true},
-        {"bandpk", "fwd u8->f32 band 4 w/cu", band_fwd<float, (P & ~(3u << 12)), 4>, 5, 4, true},
-        {"bandpk", "fwd u8->f32 band 4 w/cu packed", band_fwd<float, (P & ~(3u << 12)), 4, true>, 5, 4, true},
-        {"bandpk", "fwd u8->f32 band 8 w/cu b256 packed", band_fwd<float, (P & ~(3u << 12)), 8, true>, 5, 4, true},
+        {"bandpk", "fwd u8->f32 band 4 w/cu", band_fwd<float, with_block<256>(P), 4>, 5, 4, true},
+        {"bandpk", "fwd u8->f32 band 4 w/cu packed", band_fwd<float, with_block<256>(P), 4, true>, 5, 4, true},
+        {"bandpk", "fwd u8->f32 band 8 w/cu b256 packed", band_fwd<float, with_block<256>(P), 8, true>, 5, 4, true},
         {"bandpk", "fwd u8->f32 library (b512) again", prod_f32_fwd<P>, 5, 4, true},
-        {"bandpk", "fwd u8->f32 band 4 w/cu packed again", band_fwd<float, (P & ~(3u << 12)), 4, true>, 5, 4, true},
+        {"bandpk", "fwd u8->f32 band 4 w/cu packed again", band_fwd<float, with_block<256>(P), 4, true>, 5, 4, true},
         {"pk", "fwd u8->f32 library (b512)", prod_f32_fwd<P>, 5, 4, true},
         {"pk", "fwd u8->f32 packed (b512)", ab_fwd<float, P | ab::kVarPacked>, 5, 4, true},
-        {"pk", "fwd u8->f32 packed (b256)", ab_fwd<float, (P & ~(3u << 12)) | ab::kVarPacked>, 5, 4, true},
-        {"pk", "fwd u8->f32 packed (b1024)", ab_fwd<float, P | (3u << 12) | ab::kVarPacked>, 5, 4, true},
+        {"pk", "fwd u8->f32 packed (b256)", ab_fwd<float, with_block<256>(P) | ab::kVarPacked>, 5, 4, true},
+        {"pk", "fwd u8->f32 packed (b1024)", ab_fwd<float, with_block<1024>(P) | ab::kVarPacked>, 5, 4, true},
         {"pk", "fwd u8->f32 library (b512) again", prod_f32_fwd<P>, 5, 4, true},
         {"pk", "fwd u8->f32 packed (b512) again", ab_fwd<float, P | ab::kVarPacked>, 5, 4, true},
         {"rtpk", "rt + sums, library", rt_prod<true>, 6, 1, true},
@@ -447,7 +450,7 @@ int main(int argc, char** argv) {
         {"rtpk", "rt + sums, packed again", rt_pk<true>, 6, 1, true},
         {"pki8", "fwd u8->i8 library (b512)", prod_i8_fwd<I8>, 2, 1, true},
         {"pki8", "fwd u8->i8 packed (b512)", ab_fwd<int8_t, I8 | ab::kVarPacked>, 2, 1, true},
-        {"pki8", "fwd u8->i8 packed (b256)", ab_fwd<int8_t, (I8 & ~(3u << 12)) | ab::kVarPacked>, 2, 1, true},
+        {"pki8", "fwd u8->i8 packed (b256)", ab_fwd<int8_t, with_block<256>(I8) | ab::kVarPacked>, 2, 1, true},
         {"pki8", "fwd u8->i8 library (b512) again", prod_i8_fwd<I8>, 2, 1, true},
         {"pki8", "fwd u8->i8 packed (b512) again", ab_fwd<int8_t, I8 | ab::kVarPacked>, 2, 1, true},
         // 8 chains x 4096 steps x 2 fmas per lane pair: 65,536 fma per lane in both forms
@@ -473,27 +476,27 @@ int main(int argc, char** argv) {
         // occupancy caps (dynamic LDS): does the one-set-per-wave dispatch gain DRAM efficiency with fewer
         // waves per CU, as the banded schedule did (0.77 at 4 w/cu), and can the packed math keep up there?
         // round 5: the headline's limiter at cap 7, counters in their own passes
-        {"lim", "fwd u8->f32 product kernel, cap 7 w/cu", prod_f32_fwd_cap<530457u, 7>, 5, 4, true},
+        {"lim", "fwd u8->f32 product kernel, cap 7 w/cu", prod_f32_fwd_cap<kLimVar, 7>, 5, 4, true},
         {"lim", "pat 1-wave WGs, cap 4 w/cu", pat_grid_cap1_go<4>, 5, 4, false},
         {"lim", "pat 1-wave WGs, cap 7 w/cu", pat_grid_cap1_go<7>, 5, 4, false},
         {"lim", "pat 1-wave WGs, uncapped", pat_grid_cap1_go<0>, 5, 4, false},
-        {"lim1", "fwd u8->f32 product kernel, cap 7 w/cu", prod_f32_fwd_cap<530457u, 7>, 5, 4, true},
+        {"lim1", "fwd u8->f32 product kernel, cap 7 w/cu", prod_f32_fwd_cap<kLimVar, 7>, 5, 4, true},
         // the whole-run test hoisted out of the per-row stores (two straight-line body copies)
-        {"hoist", "fwd u8->f32 product kernel, cap 7 w/cu", prod_f32_fwd_cap<530457u, 7>, 5, 4, true},
-        {"hoist", "fwd u8->f32 hoisted run test, cap 7 w/cu", prod_f32_fwd_cap<(530457u | kVarHoistRun), 7>, 5, 4, true},
-        {"hoist", "fwd u8->f32 hoisted run test, cap 6 w/cu", prod_f32_fwd_cap<(530457u | kVarHoistRun), 6>, 5, 4, true},
-        {"hoist", "fwd u8->f32 hoisted run test, cap 8 w/cu", prod_f32_fwd_cap<(530457u | kVarHoistRun), 8>, 5, 4, true},
-        {"hoist", "fwd u8->f32 product kernel, cap 7 w/cu again", prod_f32_fwd_cap<530457u, 7>, 5, 4, true},
-        {"hoist", "fwd u8->f32 hoisted run test, cap 7 w/cu again", prod_f32_fwd_cap<(530457u | kVarHoistRun), 7>, 5, 4, true},
+        {"hoist", "fwd u8->f32 product kernel, cap 7 w/cu", prod_f32_fwd_cap<kLimVar, 7>, 5, 4, true},
+        {"hoist", "fwd u8->f32 hoisted run test, cap 7 w/cu", prod_f32_fwd_cap<(kLimVar | kVarHoistRun), 7>, 5, 4, true},
+        {"hoist", "fwd u8->f32 hoisted run test, cap 6 w/cu", prod_f32_fwd_cap<(kLimVar | kVarHoistRun), 6>, 5, 4, true},
+        {"hoist", "fwd u8->f32 hoisted run test, cap 8 w/cu", prod_f32_fwd_cap<(kLimVar | kVarHoistRun), 8>, 5, 4, true},
+        {"hoist", "fwd u8->f32 product kernel, cap 7 w/cu again", prod_f32_fwd_cap<kLimVar, 7>, 5, 4, true},
+        {"hoist", "fwd u8->f32 hoisted run test, cap 7 w/cu again", prod_f32_fwd_cap<(kLimVar | kVarHoistRun), 7>, 5, 4, true},
         // the headline without the LDS re-staging of its rows (each lane stores its tile's 32-B rows directly):
         // at <= 7 waves per CU a wave's 8 LDS round trips are poorly hidden
-        {"nolds", "fwd u8->f32 product kernel, cap 7 w/cu", prod_f32_fwd_cap<530457u, 7>, 5, 4, true},
-        {"nolds", "fwd u8->f32 no LDS staging, cap 7 w/cu", prod_f32_fwd_cap<(530457u & ~8u), 7>, 5, 4, true},
-        {"nolds", "fwd u8->f32 no LDS staging, cap 8 w/cu", prod_f32_fwd_cap<(530457u & ~8u), 8>, 5, 4, true},
-        {"nolds", "fwd u8->f32 no LDS staging, cap 10 w/cu", prod_f32_fwd_cap<(530457u & ~8u), 10>, 5, 4, true},
-        {"nolds", "fwd u8->f32 no LDS staging, cap 12 w/cu", prod_f32_fwd_cap<(530457u & ~8u), 12>, 5, 4, true},
-        {"nolds", "fwd u8->f32 product kernel, cap 7 w/cu again", prod_f32_fwd_cap<530457u, 7>, 5, 4, true},
-        {"nolds", "fwd u8->f32 no LDS staging, cap 7 w/cu again", prod_f32_fwd_cap<(530457u & ~8u), 7>, 5, 4, true},
+        {"nolds", "fwd u8->f32 product kernel, cap 7 w/cu", prod_f32_fwd_cap<kLimVar, 7>, 5, 4, true},
+        {"nolds", "fwd u8->f32 no LDS staging, cap 7 w/cu", prod_f32_fwd_cap<(kLimVar & ~8u), 7>, 5, 4, true},
+        {"nolds", "fwd u8->f32 no LDS staging, cap 8 w/cu", prod_f32_fwd_cap<(kLimVar & ~8u), 8>, 5, 4, true},
+        {"nolds", "fwd u8->f32 no LDS staging, cap 10 w/cu", prod_f32_fwd_cap<(kLimVar & ~8u), 10>, 5, 4, true},
+        {"nolds", "fwd u8->f32 no LDS staging, cap 12 w/cu", prod_f32_fwd_cap<(kLimVar & ~8u), 12>, 5, 4, true},
+        {"nolds", "fwd u8->f32 product kernel, cap 7 w/cu again", prod_f32_fwd_cap<kLimVar, 7>, 5, 4, true},
+        {"nolds", "fwd u8->f32 no LDS staging, cap 7 w/cu again", prod_f32_fwd_cap<(kLimVar & ~8u), 7>, 5, 4, true},
         {"lim4", "pat 1-wave WGs, cap 4 w/cu", pat_grid_cap1_go<4>, 5, 4, false},
         {"lim7", "pat 1-wave WGs, cap 7 w/cu", pat_grid_cap1_go<7>, 5, 4, false},
         {"occpat", "pat one set per wave (grid)", pat_grid_go, 5, 4, false},
@@ -504,33 +507,33 @@ int main(int argc, char** argv) {
         {"occpat", "pat grid cap 24 w/cu", pat_grid_cap_go<6>, 5, 4, false},
         {"occpat", "pat one set per wave (grid) again", pat_grid_go, 5, 4, false},
         {"occ", "fwd u8->f32 library (b512)", prod_f32_fwd<P>, 5, 4, true},
-        {"occ", "fwd u8->f32 scalar b256 cap 8 w/cu", ab_fwd_cap<float, (P & ~(3u << 12)), 2>, 5, 4, true},
-        {"occ", "fwd u8->f32 scalar b256 cap 12 w/cu", ab_fwd_cap<float, (P & ~(3u << 12)), 3>, 5, 4, true},
+        {"occ", "fwd u8->f32 scalar b256 cap 8 w/cu", ab_fwd_cap<float, with_block<256>(P), 2>, 5, 4, true},
+        {"occ", "fwd u8->f32 scalar b256 cap 12 w/cu", ab_fwd_cap<float, with_block<256>(P), 3>, 5, 4, true},
         {"occ", "fwd u8->f32 packed (b512)", ab_fwd<float, P | ab::kVarPacked>, 5, 4, true},
-        {"occ", "fwd u8->f32 packed b256 cap 8 w/cu", ab_fwd_cap<float, (P & ~(3u << 12)) | ab::kVarPacked, 2>, 5, 4, true},
-        {"occ", "fwd u8->f32 packed b256 cap 12 w/cu", ab_fwd_cap<float, (P & ~(3u << 12)) | ab::kVarPacked, 3>, 5, 4, true},
+        {"occ", "fwd u8->f32 packed b256 cap 8 w/cu", ab_fwd_cap<float, with_block<256>(P) | ab::kVarPacked, 2>, 5, 4, true},
+        {"occ", "fwd u8->f32 packed b256 cap 12 w/cu", ab_fwd_cap<float, with_block<256>(P) | ab::kVarPacked, 3>, 5, 4, true},
         {"occ", "fwd u8->f32 packed b512 cap 8 w/cu", ab_fwd_cap<float, P | ab::kVarPacked, 1>, 5, 4, true},
         {"occ", "fwd u8->f32 library (b512) again", prod_f32_fwd<P>, 5, 4, true},
-        {"occ", "fwd u8->f32 packed b256 cap 12 w/cu again", ab_fwd_cap<float, (P & ~(3u << 12)) | ab::kVarPacked, 3>, 5, 4, true},
+        {"occ", "fwd u8->f32 packed b256 cap 12 w/cu again", ab_fwd_cap<float, with_block<256>(P) | ab::kVarPacked, 3>, 5, 4, true},
         // round 3, session 3: finer occupancy caps (64-thread workgroups = one wave each)
         {"occ2", "fwd u8->f32 library (b512)", prod_f32_fwd<P>, 5, 4, true},
-        {"occ2", "fwd u8->f32 scalar b256 cap 12 w/cu", ab_fwd_cap<float, (P & ~(3u << 12)), 3>, 5, 4, true},
+        {"occ2", "fwd u8->f32 scalar b256 cap 12 w/cu", ab_fwd_cap<float, with_block<256>(P), 3>, 5, 4, true},
         {"occ2", "fwd u8->f32 library kernel b512 cap 8 w/cu", prod_f32_fwd_cap<P, 1>, 5, 4, true},
-        {"occ2", "fwd u8->f32 scalar b64 cap 6 w/cu", ab_fwd_cap<float, (P & ~(3u << 12)) | (1u << 12), 6>, 5, 4, true},
-        {"occ2", "fwd u8->f32 scalar b64 cap 8 w/cu", ab_fwd_cap<float, (P & ~(3u << 12)) | (1u << 12), 8>, 5, 4, true},
-        {"occ2", "fwd u8->f32 scalar b64 cap 10 w/cu", ab_fwd_cap<float, (P & ~(3u << 12)) | (1u << 12), 10>, 5, 4, true},
-        {"occ2", "fwd u8->f32 scalar b64 cap 12 w/cu", ab_fwd_cap<float, (P & ~(3u << 12)) | (1u << 12), 12>, 5, 4, true},
-        {"occ2", "fwd u8->f32 packed b64 cap 6 w/cu", ab_fwd_cap<float, (P & ~(3u << 12)) | (1u << 12) | ab::kVarPacked, 6>, 5, 4, true},
-        {"occ2", "fwd u8->f32 packed b64 cap 8 w/cu", ab_fwd_cap<float, (P & ~(3u << 12)) | (1u << 12) | ab::kVarPacked, 8>, 5, 4, true},
-        {"occ2", "fwd u8->f32 packed b256 cap 4 w/cu", ab_fwd_cap<float, (P & ~(3u << 12)) | ab::kVarPacked, 1>, 5, 4, true},
-        {"occ2", "fwd u8->f32 scalar b256 cap 8 w/cu", ab_fwd_cap<float, (P & ~(3u << 12)), 2>, 5, 4, true},
+        {"occ2", "fwd u8->f32 scalar b64 cap 6 w/cu", ab_fwd_cap<float, with_block<64>(P), 6>, 5, 4, true},
+        {"occ2", "fwd u8->f32 scalar b64 cap 8 w/cu", ab_fwd_cap<float, with_block<64>(P), 8>, 5, 4, true},
+        {"occ2", "fwd u8->f32 scalar b64 cap 10 w/cu", ab_fwd_cap<float, with_block<64>(P), 10>, 5, 4, true},
+        {"occ2", "fwd u8->f32 scalar b64 cap 12 w/cu", ab_fwd_cap<float, with_block<64>(P), 12>, 5, 4, true},
+        {"occ2", "fwd u8->f32 packed b64 cap 6 w/cu", ab_fwd_cap<float, with_block<64>(P) | ab::kVarPacked, 6>, 5, 4, true},
+        {"occ2", "fwd u8->f32 packed b64 cap 8 w/cu", ab_fwd_cap<float, with_block<64>(P) | ab::kVarPacked, 8>, 5, 4, true},
+        {"occ2", "fwd u8->f32 packed b256 cap 4 w/cu", ab_fwd_cap<float, with_block<256>(P) | ab::kVarPacked, 1>, 5, 4, true},
+        {"occ2", "fwd u8->f32 scalar b256 cap 8 w/cu", ab_fwd_cap<float, with_block<256>(P), 2>, 5, 4, true},
         {"occ2", "fwd u8->f32 library (b512) again", prod_f32_fwd<P>, 5, 4, true},
-        {"occ2", "fwd u8->f32 scalar b256 cap 12 w/cu again", ab_fwd_cap<float, (P & ~(3u << 12)), 3>, 5, 4, true},
+        {"occ2", "fwd u8->f32 scalar b256 cap 12 w/cu again", ab_fwd_cap<float, with_block<256>(P), 3>, 5, 4, true},
         {"occi8", "fwd u8->i8 library (b512)", prod_i8_fwd<I8>, 2, 1, true},
-        {"occi8", "fwd u8->i8 scalar b256 cap 12 w/cu", ab_fwd_cap<int8_t, (I8 & ~(3u << 12)), 3>, 2, 1, true},
-        {"occi8", "fwd u8->i8 scalar b256 cap 16 w/cu", ab_fwd_cap<int8_t, (I8 & ~(3u << 12)), 4>, 2, 1, true},
-        {"occi8", "fwd u8->i8 packed b256 cap 12 w/cu", ab_fwd_cap<int8_t, (I8 & ~(3u << 12)) | ab::kVarPacked, 3>, 2, 1, true},
-        {"occi8", "fwd u8->i8 packed b256 cap 8 w/cu", ab_fwd_cap<int8_t, (I8 & ~(3u << 12)) | ab::kVarPacked, 2>, 2, 1, true},
+        {"occi8", "fwd u8->i8 scalar b256 cap 12 w/cu", ab_fwd_cap<int8_t, with_block<256>(I8), 3>, 2, 1, true},
+        {"occi8", "fwd u8->i8 scalar b256 cap 16 w/cu", ab_fwd_cap<int8_t, with_block<256>(I8), 4>, 2, 1, true},
+        {"occi8", "fwd u8->i8 packed b256 cap 12 w/cu", ab_fwd_cap<int8_t, with_block<256>(I8) | ab::kVarPacked, 3>, 2, 1, true},
+        {"occi8", "fwd u8->i8 packed b256 cap 8 w/cu", ab_fwd_cap<int8_t, with_block<256>(I8) | ab::kVarPacked, 2>, 2, 1, true},
         {"occi8", "fwd u8->i8 library (b512) again", prod_i8_fwd<I8>, 2, 1, true},
         {"rtocc", "rt + sums, library", rt_cap<true, 0>, 6, 1, true},
         {"rtocc", "rt + sums, cap 8 w/cu", rt_cap<true, 1>, 6, 1, true},
@@ -545,61 +548,61 @@ int main(int argc, char** argv) {
         {"invocc", "inv f32->f32 duo library again", inv_cap<0>, 8, 4, true},
         // round 3, session 3: 1-wave workgroups, occupancy caps (sweep; also run at other frame sizes)
         {"occsz", "fwd u8->f32 library", prod_f32_fwd<P>, 5, 4, true},
-        {"occsz", "fwd u8->f32 scalar b64 uncapped", ab_fwd<float, (P & ~(3u << 12)) | (1u << 12)>, 5, 4, true},
-        {"occsz", "fwd u8->f32 scalar b64 cap 8 w/cu", ab_fwd_cap<float, (P & ~(3u << 12)) | (1u << 12), 8>, 5, 4, true},
-        {"occsz", "fwd u8->f32 scalar b64 cap 9 w/cu", ab_fwd_cap<float, (P & ~(3u << 12)) | (1u << 12), 9>, 5, 4, true},
-        {"occsz", "fwd u8->f32 scalar b64 cap 10 w/cu", ab_fwd_cap<float, (P & ~(3u << 12)) | (1u << 12), 10>, 5, 4, true},
-        {"occsz", "fwd u8->f32 scalar b64 cap 11 w/cu", ab_fwd_cap<float, (P & ~(3u << 12)) | (1u << 12), 11>, 5, 4, true},
-        {"occsz", "fwd u8->f32 scalar b64 cap 12 w/cu", ab_fwd_cap<float, (P & ~(3u << 12)) | (1u << 12), 12>, 5, 4, true},
-        {"occsz", "fwd u8->f32 packed b64 cap 8 w/cu", ab_fwd_cap<float, (P & ~(3u << 12)) | (1u << 12) | ab::kVarPacked, 8>, 5, 4, true},
-        {"occsz", "fwd u8->f32 packed b64 cap 10 w/cu", ab_fwd_cap<float, (P & ~(3u << 12)) | (1u << 12) | ab::kVarPacked, 10>, 5, 4, true},
+        {"occsz", "fwd u8->f32 scalar b64 uncapped", ab_fwd<float, with_block<64>(P)>, 5, 4, true},
+        {"occsz", "fwd u8->f32 scalar b64 cap 8 w/cu", ab_fwd_cap<float, with_block<64>(P), 8>, 5, 4, true},
+        {"occsz", "fwd u8->f32 scalar b64 cap 9 w/cu", ab_fwd_cap<float, with_block<64>(P), 9>, 5, 4, true},
+        {"occsz", "fwd u8->f32 scalar b64 cap 10 w/cu", ab_fwd_cap<float, with_block<64>(P), 10>, 5, 4, true},
+        {"occsz", "fwd u8->f32 scalar b64 cap 11 w/cu", ab_fwd_cap<float, with_block<64>(P), 11>, 5, 4, true},
+        {"occsz", "fwd u8->f32 scalar b64 cap 12 w/cu", ab_fwd_cap<float, with_block<64>(P), 12>, 5, 4, true},
+        {"occsz", "fwd u8->f32 packed b64 cap 8 w/cu", ab_fwd_cap<float, with_block<64>(P) | ab::kVarPacked, 8>, 5, 4, true},
+        {"occsz", "fwd u8->f32 packed b64 cap 10 w/cu", ab_fwd_cap<float, with_block<64>(P) | ab::kVarPacked, 10>, 5, 4, true},
         {"occsz", "fwd u8->f32 library again", prod_f32_fwd<P>, 5, 4, true},
-        {"occsz", "fwd u8->f32 scalar b64 cap 10 w/cu again", ab_fwd_cap<float, (P & ~(3u << 12)) | (1u << 12), 10>, 5, 4, true},
-        {"occsz", "fwd u8->f32 packed b64 cap 8 w/cu again", ab_fwd_cap<float, (P & ~(3u << 12)) | (1u << 12) | ab::kVarPacked, 8>, 5, 4, true},
+        {"occsz", "fwd u8->f32 scalar b64 cap 10 w/cu again", ab_fwd_cap<float, with_block<64>(P), 10>, 5, 4, true},
+        {"occsz", "fwd u8->f32 packed b64 cap 8 w/cu again", ab_fwd_cap<float, with_block<64>(P) | ab::kVarPacked, 8>, 5, 4, true},
         {"occi8b", "fwd u8->i8 library (b512)", prod_i8_fwd<I8>, 2, 1, true},
-        {"occi8b", "fwd u8->i8 scalar b64 uncapped", ab_fwd<int8_t, (I8 & ~(3u << 12)) | (1u << 12)>, 2, 1, true},
-        {"occi8b", "fwd u8->i8 scalar b64 cap 12 w/cu", ab_fwd_cap<int8_t, (I8 & ~(3u << 12)) | (1u << 12), 12>, 2, 1, true},
-        {"occi8b", "fwd u8->i8 scalar b64 cap 16 w/cu", ab_fwd_cap<int8_t, (I8 & ~(3u << 12)) | (1u << 12), 16>, 2, 1, true},
-        {"occi8b", "fwd u8->i8 packed b64 cap 16 w/cu", ab_fwd_cap<int8_t, (I8 & ~(3u << 12)) | (1u << 12) | ab::kVarPacked, 16>, 2, 1, true},
+        {"occi8b", "fwd u8->i8 scalar b64 uncapped", ab_fwd<int8_t, with_block<64>(I8)>, 2, 1, true},
+        {"occi8b", "fwd u8->i8 scalar b64 cap 12 w/cu", ab_fwd_cap<int8_t, with_block<64>(I8), 12>, 2, 1, true},
+        {"occi8b", "fwd u8->i8 scalar b64 cap 16 w/cu", ab_fwd_cap<int8_t, with_block<64>(I8), 16>, 2, 1, true},
+        {"occi8b", "fwd u8->i8 packed b64 cap 16 w/cu", ab_fwd_cap<int8_t, with_block<64>(I8) | ab::kVarPacked, 16>, 2, 1, true},
         {"occi8b", "fwd u8->i8 library (b512) again", prod_i8_fwd<I8>, 2, 1, true},
         {"invb", "inv f32->f32 duo library", inv_cap<0>, 8, 4, true},
         {"invb", "inv f32->f32 duo b256 cap 8 w/cu", inv_cap<2>, 8, 4, true},
         {"invb", "inv f32->f32 duo b256 cap 12 w/cu", inv_cap<3>, 8, 4, true},
-        {"invb", "inv f32->f32 duo b64 uncapped", inv_cap_v<kDuoVar | (1u << 12), 0>, 8, 4, true},
-        {"invb", "inv f32->f32 duo b64 cap 8 w/cu", inv_cap_v<kDuoVar | (1u << 12), 8>, 8, 4, true},
-        {"invb", "inv f32->f32 duo b64 cap 10 w/cu", inv_cap_v<kDuoVar | (1u << 12), 10>, 8, 4, true},
-        {"invb", "inv f32->f32 duo b64 cap 12 w/cu", inv_cap_v<kDuoVar | (1u << 12), 12>, 8, 4, true},
+        {"invb", "inv f32->f32 duo b64 uncapped", inv_cap_v<with_block<64>(kDuoVar), 0>, 8, 4, true},
+        {"invb", "inv f32->f32 duo b64 cap 8 w/cu", inv_cap_v<with_block<64>(kDuoVar), 8>, 8, 4, true},
+        {"invb", "inv f32->f32 duo b64 cap 10 w/cu", inv_cap_v<with_block<64>(kDuoVar), 10>, 8, 4, true},
+        {"invb", "inv f32->f32 duo b64 cap 12 w/cu", inv_cap_v<with_block<64>(kDuoVar), 12>, 8, 4, true},
         {"invb", "inv f32->f32 duo library again", inv_cap<0>, 8, 4, true},
         {"dropin", "dropin fwd f32 duo library", dropin_fwd_cap<kDuoVar, 0>, 12, 4, true},
         {"dropin", "dropin fwd f32 duo b256 cap 8 w/cu", dropin_fwd_cap<kDuoVar, 2>, 12, 4, true},
         {"dropin", "dropin fwd f32 duo b256 cap 12 w/cu", dropin_fwd_cap<kDuoVar, 3>, 12, 4, true},
-        {"dropin", "dropin fwd f32 duo b64 cap 8 w/cu", dropin_fwd_cap<kDuoVar | (1u << 12), 8>, 12, 4, true},
-        {"dropin", "dropin fwd f32 duo b64 cap 10 w/cu", dropin_fwd_cap<kDuoVar | (1u << 12), 10>, 12, 4, true},
-        {"dropin", "dropin fwd f32 duo b64 cap 12 w/cu", dropin_fwd_cap<kDuoVar | (1u << 12), 12>, 12, 4, true},
+        {"dropin", "dropin fwd f32 duo b64 cap 8 w/cu", dropin_fwd_cap<with_block<64>(kDuoVar), 8>, 12, 4, true},
+        {"dropin", "dropin fwd f32 duo b64 cap 10 w/cu", dropin_fwd_cap<with_block<64>(kDuoVar), 10>, 12, 4, true},
+        {"dropin", "dropin fwd f32 duo b64 cap 12 w/cu", dropin_fwd_cap<with_block<64>(kDuoVar), 12>, 12, 4, true},
         {"dropin", "dropin fwd f32 duo library again", dropin_fwd_cap<kDuoVar, 0>, 12, 4, true},
         {"c2oct", "octet 256-thread WGs (library)", oct_f32_fwd<kOctVar<float> | kVarFastDiv>, 5, 4, true},
-        {"c2oct", "octet 512-thread WGs", oct_f32_fwd<(kOctVar<float> | kVarFastDiv) | (2u << 12)>, 5, 4, true},
-        {"c2oct", "octet 1024-thread WGs", oct_f32_fwd<(kOctVar<float> | kVarFastDiv) | (3u << 12)>, 5, 4, true},
+        {"c2oct", "octet 512-thread WGs", oct_f32_fwd<with_block<512>(kOctVar<float> | kVarFastDiv)>, 5, 4, true},
+        {"c2oct", "octet 1024-thread WGs", oct_f32_fwd<with_block<1024>(kOctVar<float> | kVarFastDiv)>, 5, 4, true},
         {"c2oct", "octet 256-thread WGs again", oct_f32_fwd<kOctVar<float> | kVarFastDiv>, 5, 4, true},
-        {"c2oct", "tile 1024-thread WGs (the library's above 8 sets/CU)", prod_f32_fwd<((kProdVar<uint8_t, float> | kVarFastDiv | kVarJpegQ) & ~(3u << 12)) | (3u << 12)>, 5, 4, true},
+        {"c2oct", "tile 1024-thread WGs (the library's above 8 sets/CU)", prod_f32_fwd<with_block<1024>(kProdVar<uint8_t, float> | kVarFastDiv | kVarJpegQ)>, 5, 4, true},
         {"dropcap", "dropin uncapped (round 5)", dropin_fwd_rt<kDuoVar | kVarFastDivChecked, 0>, 12, 4, true},
-        {"dropcap", "dropin b64 cap 10", dropin_fwd_rt<kDuoVar | kVarFastDivChecked | (1u << 12), 10>, 12, 4, true},
-        {"dropcap", "dropin b64 cap 8", dropin_fwd_rt<kDuoVar | kVarFastDivChecked | (1u << 12), 8>, 12, 4, true},
-        {"dropcap", "dropin b64 cap 10 again", dropin_fwd_rt<kDuoVar | kVarFastDivChecked | (1u << 12), 10>, 12, 4, true},
+        {"dropcap", "dropin b64 cap 10", dropin_fwd_rt<with_block<64>(kDuoVar | kVarFastDivChecked), 10>, 12, 4, true},
+        {"dropcap", "dropin b64 cap 8", dropin_fwd_rt<with_block<64>(kDuoVar | kVarFastDivChecked), 8>, 12, 4, true},
+        {"dropcap", "dropin b64 cap 10 again", dropin_fwd_rt<with_block<64>(kDuoVar | kVarFastDivChecked), 10>, 12, 4, true},
         {"dropcap", "dropin uncapped again", dropin_fwd_rt<kDuoVar | kVarFastDivChecked, 0>, 12, 4, true},
         {"fwdcap", "fwd no wb uncapped (round 5)", dropin_fwd_rt<kDuoVar | kVarFastDivChecked, 0, false>, 8, 4, true},
-        {"fwdcap", "fwd no wb b64 cap 10", dropin_fwd_rt<kDuoVar | kVarFastDivChecked | (1u << 12), 10, false>, 8, 4, true},
+        {"fwdcap", "fwd no wb b64 cap 10", dropin_fwd_rt<with_block<64>(kDuoVar | kVarFastDivChecked), 10, false>, 8, 4, true},
         {"fwdcap", "fwd no wb uncapped again", dropin_fwd_rt<kDuoVar | kVarFastDivChecked, 0, false>, 8, 4, true},
         // round 6, after the duo forward's 16-wave cap: the fp32 duo forward in 256-thread workgroups
-        {"duocap16", "dropin b64 cap 10 (product)", dropin_fwd_rt<kDuoVar | kVarFastDivChecked | (1u << 12), 10>, 12, 4, true},
-        {"duocap16", "dropin b64 cap 16", dropin_fwd_rt<kDuoVar | kVarFastDivChecked | (1u << 12), 16>, 12, 4, true},
-        {"duocap16", "dropin b64 cap 6", dropin_fwd_rt<kDuoVar | kVarFastDivChecked | (1u << 12), 6>, 12, 4, true},
-        {"duocap16", "dropin b256 cap 4 WGs", dropin_fwd_rt<(kDuoVar | kVarFastDivChecked) & ~(3u << 12), 4>, 12, 4, true},
-        {"duocap16", "dropin b256 cap 3 WGs", dropin_fwd_rt<(kDuoVar | kVarFastDivChecked) & ~(3u << 12), 3>, 12, 4, true},
-        {"duocap16", "fwd no wb b64 cap 10 (product)", dropin_fwd_rt<kDuoVar | kVarFastDivChecked | (1u << 12), 10, false>, 8, 4, true},
-        {"duocap16", "fwd no wb b256 cap 4 WGs", dropin_fwd_rt<(kDuoVar | kVarFastDivChecked) & ~(3u << 12), 4, false>, 8, 4, true},
-        {"duocap16", "dropin b64 cap 10 (product) again", dropin_fwd_rt<kDuoVar | kVarFastDivChecked | (1u << 12), 10>, 12, 4, true},
-        {"duocap16", "dropin b256 cap 4 WGs again", dropin_fwd_rt<(kDuoVar | kVarFastDivChecked) & ~(3u << 12), 4>, 12, 4, true},
+        {"duocap16", "dropin b64 cap 10 (product)", dropin_fwd_rt<with_block<64>(kDuoVar | kVarFastDivChecked), 10>, 12, 4, true},
+        {"duocap16", "dropin b64 cap 16", dropin_fwd_rt<with_block<64>(kDuoVar | kVarFastDivChecked), 16>, 12, 4, true},
+        {"duocap16", "dropin b64 cap 6", dropin_fwd_rt<with_block<64>(kDuoVar | kVarFastDivChecked), 6>, 12, 4, true},
+        {"duocap16", "dropin b256 cap 4 WGs", dropin_fwd_rt<with_block<256>(kDuoVar | kVarFastDivChecked), 4>, 12, 4, true},
+        {"duocap16", "dropin b256 cap 3 WGs", dropin_fwd_rt<with_block<256>(kDuoVar | kVarFastDivChecked), 3>, 12, 4, true},
+        {"duocap16", "fwd no wb b64 cap 10 (product)", dropin_fwd_rt<with_block<64>(kDuoVar | kVarFastDivChecked), 10, false>, 8, 4, true},
+        {"duocap16", "fwd no wb b256 cap 4 WGs", dropin_fwd_rt<with_block<256>(kDuoVar | kVarFastDivChecked), 4, false>, 8, 4, true},
+        {"duocap16", "dropin b64 cap 10 (product) again", dropin_fwd_rt<with_block<64>(kDuoVar | kVarFastDivChecked), 10>, 12, 4, true},
+        {"duocap16", "dropin b256 cap 4 WGs again", dropin_fwd_rt<with_block<256>(kDuoVar | kVarFastDivChecked), 4>, 12, 4, true},
         // round 4: the default JPEG table's per-position 3-op quantiser forms (kVarJpegQ) against the
         // verified 6-op form, in the product's dispatch, and the headline cap re-swept with them
         {"jq", "fwd u8->f32 library cap 10 (6-op)", prod_f32_fwd_cap<PK1, 10>, 5, 4, true},
@@ -611,34 +614,34 @@ int main(int argc, char** argv) {
         {"jq", "fwd u8->f32 jpegq cap 10 w/cu again", prod_f32_fwd_cap<PK1 | kVarJpegQ, 10>, 5, 4, true},
         {"jqi8", "fwd u8->i8 library b512 (6-op)", prod_i8_fwd<I8>, 2, 1, true},
         {"jqi8", "fwd u8->i8 jpegq b512", prod_i8_fwd<I8 | kVarJpegQ>, 2, 1, true},
-        {"jqi8", "fwd u8->i8 jpegq b256", prod_i8_fwd<(I8 & ~(3u << 12)) | kVarJpegQ>, 2, 1, true},
-        {"jqi8", "fwd u8->i8 jpegq b1024", prod_i8_fwd<(I8 & ~(3u << 12)) | (3u << 12) | kVarJpegQ>, 2, 1, true},
-        {"jqi8", "fwd u8->i8 jpegq b64 cap 16 w/cu", prod_i8_fwd_cap<(I8 & ~(3u << 12)) | (1u << 12) | kVarJpegQ, 16>, 2, 1, true},
+        {"jqi8", "fwd u8->i8 jpegq b256", prod_i8_fwd<with_block<256>(I8) | kVarJpegQ>, 2, 1, true},
+        {"jqi8", "fwd u8->i8 jpegq b1024", prod_i8_fwd<with_block<1024>(I8) | kVarJpegQ>, 2, 1, true},
+        {"jqi8", "fwd u8->i8 jpegq b64 cap 16 w/cu", prod_i8_fwd_cap<with_block<64>(I8) | kVarJpegQ, 16>, 2, 1, true},
         {"jqi8", "fwd u8->i8 jpegq packed b512", prod_i8_fwd<I8 | kVarJpegQ | kVarPacked>, 2, 1, true},
-        {"jqi8", "fwd u8->i8 jpegq packed b256", prod_i8_fwd<(I8 & ~(3u << 12)) | kVarJpegQ | kVarPacked>, 2, 1, true},
-        {"jqi8", "fwd u8->i8 jpegq packed b64 cap 16 w/cu", prod_i8_fwd_cap<(I8 & ~(3u << 12)) | (1u << 12) | kVarJpegQ | kVarPacked, 16>, 2, 1, true},
+        {"jqi8", "fwd u8->i8 jpegq packed b256", prod_i8_fwd<with_block<256>(I8) | kVarJpegQ | kVarPacked>, 2, 1, true},
+        {"jqi8", "fwd u8->i8 jpegq packed b64 cap 16 w/cu", prod_i8_fwd_cap<with_block<64>(I8) | kVarJpegQ | kVarPacked, 16>, 2, 1, true},
         {"jqi8", "fwd u8->i8 library b512 (6-op) again", prod_i8_fwd<I8>, 2, 1, true},
         {"jqi8", "fwd u8->i8 jpegq b512 again", prod_i8_fwd<I8 | kVarJpegQ>, 2, 1, true},
         // round 4, session 2: the packed int8 forward (JPEG forms and the 6-op quotient) across block sizes / caps
         {"jqi8b", "fwd u8->i8 library b512 (6-op)", prod_i8_fwd<I8>, 2, 1, true},
         {"jqi8b", "fwd u8->i8 packed 6-op b512", prod_i8_fwd<I8 | kVarPacked>, 2, 1, true},
         {"jqi8b", "fwd u8->i8 jpegq packed b512", prod_i8_fwd<I8 | kVarJpegQ | kVarPacked>, 2, 1, true},
-        {"jqi8b", "fwd u8->i8 jpegq packed b1024", prod_i8_fwd<(I8 & ~(3u << 12)) | (3u << 12) | kVarJpegQ | kVarPacked>, 2, 1, true},
-        {"jqi8b", "fwd u8->i8 jpegq packed b64 cap 8 w/cu", prod_i8_fwd_cap<(I8 & ~(3u << 12)) | (1u << 12) | kVarJpegQ | kVarPacked, 8>, 2, 1, true},
-        {"jqi8b", "fwd u8->i8 jpegq packed b64 cap 12 w/cu", prod_i8_fwd_cap<(I8 & ~(3u << 12)) | (1u << 12) | kVarJpegQ | kVarPacked, 12>, 2, 1, true},
-        {"jqi8b", "fwd u8->i8 jpegq packed b64 cap 20 w/cu", prod_i8_fwd_cap<(I8 & ~(3u << 12)) | (1u << 12) | kVarJpegQ | kVarPacked, 20>, 2, 1, true},
-        {"jqi8b", "fwd u8->i8 jpegq packed b64 uncapped", prod_i8_fwd_cap<(I8 & ~(3u << 12)) | (1u << 12) | kVarJpegQ | kVarPacked, 0>, 2, 1, true},
+        {"jqi8b", "fwd u8->i8 jpegq packed b1024", prod_i8_fwd<with_block<1024>(I8) | kVarJpegQ | kVarPacked>, 2, 1, true},
+        {"jqi8b", "fwd u8->i8 jpegq packed b64 cap 8 w/cu", prod_i8_fwd_cap<with_block<64>(I8) | kVarJpegQ | kVarPacked, 8>, 2, 1, true},
+        {"jqi8b", "fwd u8->i8 jpegq packed b64 cap 12 w/cu", prod_i8_fwd_cap<with_block<64>(I8) | kVarJpegQ | kVarPacked, 12>, 2, 1, true},
+        {"jqi8b", "fwd u8->i8 jpegq packed b64 cap 20 w/cu", prod_i8_fwd_cap<with_block<64>(I8) | kVarJpegQ | kVarPacked, 20>, 2, 1, true},
+        {"jqi8b", "fwd u8->i8 jpegq packed b64 uncapped", prod_i8_fwd_cap<with_block<64>(I8) | kVarJpegQ | kVarPacked, 0>, 2, 1, true},
         {"jqi8b", "fwd u8->i8 library b512 (6-op) again", prod_i8_fwd<I8>, 2, 1, true},
         {"jqi8b", "fwd u8->i8 jpegq packed b512 again", prod_i8_fwd<I8 | kVarJpegQ | kVarPacked>, 2, 1, true},
         // round 4, session 3: int8 block sizes with and without the JPEG forms; headline cap 7 vs 10 repeated
-        {"jqi8c", "fwd u8->i8 6-op b512", prod_i8_fwd<(I8 & ~(3u << 12)) | (2u << 12)>, 2, 1, true},
-        {"jqi8c", "fwd u8->i8 6-op b256", prod_i8_fwd<(I8 & ~(3u << 12))>, 2, 1, true},
-        {"jqi8c", "fwd u8->i8 jpegq b512", prod_i8_fwd<(I8 & ~(3u << 12)) | (2u << 12) | kVarJpegQ>, 2, 1, true},
-        {"jqi8c", "fwd u8->i8 jpegq b256", prod_i8_fwd<(I8 & ~(3u << 12)) | kVarJpegQ>, 2, 1, true},
-        {"jqi8c", "fwd u8->i8 jpegq b64 uncapped", prod_i8_fwd<(I8 & ~(3u << 12)) | (1u << 12) | kVarJpegQ>, 2, 1, true},
-        {"jqi8c", "fwd u8->i8 6-op b256 again", prod_i8_fwd<(I8 & ~(3u << 12))>, 2, 1, true},
-        {"jqi8c", "fwd u8->i8 jpegq b256 again", prod_i8_fwd<(I8 & ~(3u << 12)) | kVarJpegQ>, 2, 1, true},
-        {"jqi8c", "fwd u8->i8 jpegq b512 again", prod_i8_fwd<(I8 & ~(3u << 12)) | (2u << 12) | kVarJpegQ>, 2, 1, true},
+        {"jqi8c", "fwd u8->i8 6-op b512", prod_i8_fwd<with_block<512>(I8)>, 2, 1, true},
+        {"jqi8c", "fwd u8->i8 6-op b256", prod_i8_fwd<with_block<256>(I8)>, 2, 1, true},
+        {"jqi8c", "fwd u8->i8 jpegq b512", prod_i8_fwd<with_block<512>(I8) | kVarJpegQ>, 2, 1, true},
+        {"jqi8c", "fwd u8->i8 jpegq b256", prod_i8_fwd<with_block<256>(I8) | kVarJpegQ>, 2, 1, true},
+        {"jqi8c", "fwd u8->i8 jpegq b64 uncapped", prod_i8_fwd<with_block<64>(I8) | kVarJpegQ>, 2, 1, true},
+        {"jqi8c", "fwd u8->i8 6-op b256 again", prod_i8_fwd<with_block<256>(I8)>, 2, 1, true},
+        {"jqi8c", "fwd u8->i8 jpegq b256 again", prod_i8_fwd<with_block<256>(I8) | kVarJpegQ>, 2, 1, true},
+        {"jqi8c", "fwd u8->i8 jpegq b512 again", prod_i8_fwd<with_block<512>(I8) | kVarJpegQ>, 2, 1, true},
         {"jqcap", "fwd u8->f32 jpegq cap 10 w/cu", prod_f32_fwd_cap<PK1 | kVarJpegQ, 10>, 5, 4, true},
         {"jqcap", "fwd u8->f32 jpegq cap 7 w/cu", prod_f32_fwd_cap<PK1 | kVarJpegQ, 7>, 5, 4, true},
         {"jqcap", "fwd u8->f32 jpegq cap 9 w/cu", prod_f32_fwd_cap<PK1 | kVarJpegQ, 9>, 5, 4, true},
@@ -651,27 +654,27 @@ int main(int argc, char** argv) {
         {"capsz", "fwd u8->f32 jpegq cap 8 w/cu", prod_f32_fwd_cap<PK1 | kVarJpegQ, 8>, 5, 4, true},
         {"capsz", "fwd u8->f32 jpegq cap 10 w/cu", prod_f32_fwd_cap<PK1 | kVarJpegQ, 10>, 5, 4, true},
         {"capsz", "fwd u8->f32 jpegq cap 12 w/cu", prod_f32_fwd_cap<PK1 | kVarJpegQ, 12>, 5, 4, true},
-        {"capsz", "fwd u8->f32 jpegq scalar b1024 uncapped", prod_f32_fwd<(P & ~(3u << 12)) | (3u << 12) | kVarJpegQ>, 5, 4, true},
+        {"capsz", "fwd u8->f32 jpegq scalar b1024 uncapped", prod_f32_fwd<with_block<1024>(P) | kVarJpegQ>, 5, 4, true},
         {"capsz", "fwd u8->f32 jpegq cap 7 w/cu again", prod_f32_fwd_cap<PK1 | kVarJpegQ, 7>, 5, 4, true},
         {"capsz", "fwd u8->f32 jpegq cap 12 w/cu again", prod_f32_fwd_cap<PK1 | kVarJpegQ, 12>, 5, 4, true},
         // round 4, session 5: the fp32 duo inverse's cap below 10 (the headline moved from 10 to 7)
-        {"invc", "inv f32->f32 duo b64 cap 10 w/cu (product)", inv_cap_v<kDuoVar | (1u << 12), 10>, 8, 4, true},
-        {"invc", "inv f32->f32 duo b64 cap 6 w/cu", inv_cap_v<kDuoVar | (1u << 12), 6>, 8, 4, true},
-        {"invc", "inv f32->f32 duo b64 cap 7 w/cu", inv_cap_v<kDuoVar | (1u << 12), 7>, 8, 4, true},
-        {"invc", "inv f32->f32 duo b64 cap 8 w/cu", inv_cap_v<kDuoVar | (1u << 12), 8>, 8, 4, true},
-        {"invc", "inv f32->f32 duo b64 cap 10 w/cu again", inv_cap_v<kDuoVar | (1u << 12), 10>, 8, 4, true},
-        {"invc", "inv f32->f32 duo b64 cap 7 w/cu again", inv_cap_v<kDuoVar | (1u << 12), 7>, 8, 4, true},
-        {"invc", "inv f32->f32 duo b64 cap 8 w/cu again", inv_cap_v<kDuoVar | (1u << 12), 8>, 8, 4, true},
+        {"invc", "inv f32->f32 duo b64 cap 10 w/cu (product)", inv_cap_v<with_block<64>(kDuoVar), 10>, 8, 4, true},
+        {"invc", "inv f32->f32 duo b64 cap 6 w/cu", inv_cap_v<with_block<64>(kDuoVar), 6>, 8, 4, true},
+        {"invc", "inv f32->f32 duo b64 cap 7 w/cu", inv_cap_v<with_block<64>(kDuoVar), 7>, 8, 4, true},
+        {"invc", "inv f32->f32 duo b64 cap 8 w/cu", inv_cap_v<with_block<64>(kDuoVar), 8>, 8, 4, true},
+        {"invc", "inv f32->f32 duo b64 cap 10 w/cu again", inv_cap_v<with_block<64>(kDuoVar), 10>, 8, 4, true},
+        {"invc", "inv f32->f32 duo b64 cap 7 w/cu again", inv_cap_v<with_block<64>(kDuoVar), 7>, 8, 4, true},
+        {"invc", "inv f32->f32 duo b64 cap 8 w/cu again", inv_cap_v<with_block<64>(kDuoVar), 8>, 8, 4, true},
         // int8 forward, one-wave workgroups at higher caps (VALU-bound: needs waves)
         {"i8cap", "fwd u8->i8 jpegq b256 (product)", prod_i8_fwd<I8 | kVarJpegQ>, 2, 1, true},
-        {"i8cap", "fwd u8->i8 jpegq b64 cap 16 w/cu", prod_i8_fwd_cap<(I8 & ~(3u << 12)) | (1u << 12) | kVarJpegQ, 16>, 2, 1, true},
-        {"i8cap", "fwd u8->i8 jpegq b64 cap 20 w/cu", prod_i8_fwd_cap<(I8 & ~(3u << 12)) | (1u << 12) | kVarJpegQ, 20>, 2, 1, true},
-        {"i8cap", "fwd u8->i8 jpegq b64 cap 24 w/cu", prod_i8_fwd_cap<(I8 & ~(3u << 12)) | (1u << 12) | kVarJpegQ, 24>, 2, 1, true},
-        {"i8cap", "fwd u8->i8 jpegq b256 cap 24 w/cu", prod_i8_fwd_cap<(I8 & ~(3u << 12)) | kVarJpegQ, 6>, 2, 1, true},
+        {"i8cap", "fwd u8->i8 jpegq b64 cap 16 w/cu", prod_i8_fwd_cap<with_block<64>(I8) | kVarJpegQ, 16>, 2, 1, true},
+        {"i8cap", "fwd u8->i8 jpegq b64 cap 20 w/cu", prod_i8_fwd_cap<with_block<64>(I8) | kVarJpegQ, 20>, 2, 1, true},
+        {"i8cap", "fwd u8->i8 jpegq b64 cap 24 w/cu", prod_i8_fwd_cap<with_block<64>(I8) | kVarJpegQ, 24>, 2, 1, true},
+        {"i8cap", "fwd u8->i8 jpegq b256 cap 24 w/cu", prod_i8_fwd_cap<with_block<256>(I8) | kVarJpegQ, 6>, 2, 1, true},
         {"i8cap", "fwd u8->i8 jpegq b256 (product) again", prod_i8_fwd<I8 | kVarJpegQ>, 2, 1, true},
-        {"i8cap", "fwd u8->i8 jpegq b64 cap 20 w/cu again", prod_i8_fwd_cap<(I8 & ~(3u << 12)) | (1u << 12) | kVarJpegQ, 20>, 2, 1, true},
+        {"i8cap", "fwd u8->i8 jpegq b64 cap 20 w/cu again", prod_i8_fwd_cap<with_block<64>(I8) | kVarJpegQ, 20>, 2, 1, true},
         // the u8 -> int8 product alone, for counter passes (tools/gpu_session.sh pmcsq:...:i8lim)
-        {"i8lim", "fwd u8->i8 jpegq b64 cap 20 w/cu (product)", prod_i8_fwd_cap<(I8 & ~(3u << 12)) | (1u << 12) | kVarJpegQ, 20>, 2, 1, true},
+        {"i8lim", "fwd u8->i8 jpegq b64 cap 20 w/cu (product)", prod_i8_fwd_cap<with_block<64>(I8) | kVarJpegQ, 20>, 2, 1, true},
         // round trip workgroup size
         {"jqrtb", "rt + sums, jpegq b512", rt_q<true, 2>, 6, 1, true},
         {"jqrtb", "rt + sums, jpegq b256", rt_qb<true, 2, 256>, 6, 1, true},
@@ -760,7 +763,7 @@ int main(int argc, char** argv) {
         CK(hipMemset(g_sums_ring, 0, kRing * sizeof(RtSums)));
         // the inverse's input: each set's quantised coefficients (the forward of its frame)
         for (int k = 0; k < nsets; ++k) hipLaunchKernelGGL((hpdct::fdct_kernel<uint8_t, float, true, true, false, kProdVar<uint8_t, float> | kVarFastDiv>),
-                                                           grid_for(c.g, false, c.cus, 512), dim3(512), 0, 0, img[k], g_coef[k], nullptr, c.g, nullptr, c.qp, 128.0f);
+                                                           grid_for(c.g, 512), dim3(512), 0, 0, img[k], g_coef[k], nullptr, c.g, nullptr, c.qp, 128.0f);
     }
     CK(hipDeviceSynchronize());
     if (want_rt) {  // coefficients and sums of the packed round trip == the library's, set 1

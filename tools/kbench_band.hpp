@@ -89,7 +89,7 @@ __global__ __launch_bounds__(kBlock<kVar>, 1) void fdct_band_kernel(const uint8_
         fdct_tile(T, x, [&](auto v, float (&c)[8]) {
             if constexpr (std::is_same_v<TOut, int8_t> && (kVar & kVarI8Pack) != 0) {
                 unroll<8>([&](auto u) { c[u] = quotient<kVar>(c[u], qp.q.v[v * 8 + u], qp.r.v[v * 8 + u]); });
-                const uint2 w = make_uint2(pack_q_i8x4(c[0], c[1], c[2], c[3]), pack_q_i8x4(c[4], c[5], c[6], c[7]));
+                const uint2 w = make_uint2(ab::pack_q_i8x4(c[0], c[1], c[2], c[3]), ab::pack_q_i8x4(c[4], c[5], c[6], c[7]));
                 st<(kVar & kVarNT) != 0>(reinterpret_cast<uint2*>(out + p.base + v * g.width), w);
                 return;
             }

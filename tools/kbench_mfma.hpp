@@ -138,7 +138,7 @@ __global__ __launch_bounds__(kMfmaBlock, 1) void fdct_mfma_i8_kernel(const uint8
                 unroll<8>([&](auto i) { s = T.template mac<u * 8 + i>(p[i], s); });
                 c[u] = quotient<kFast ? kVarFastDiv : 0u>(s, qv[u], rv[u]);
             });
-            const uint2 wv = make_uint2(pack_q_i8x4(c[0], c[1], c[2], c[3]), pack_q_i8x4(c[4], c[5], c[6], c[7]));
+            const uint2 wv = make_uint2(ab::pack_q_i8x4(c[0], c[1], c[2], c[3]), ab::pack_q_i8x4(c[4], c[5], c[6], c[7]));
             st<true>(reinterpret_cast<uint2*>(orow + grp * 64u), wv);
         });
     });

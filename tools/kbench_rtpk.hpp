@@ -64,7 +64,7 @@ template <bool kStats>
 __global__ __launch_bounds__(512, 2) void roundtrip_pk_kernel(const uint8_t* __restrict__ img, float* __restrict__ coef,
                                                               uint8_t* __restrict__ recon, RtSums* __restrict__ sums,
                                                               TileGrid g, QParams qp) {
-    constexpr unsigned kVar = (2u << 12) | kVarNT | kVarLdsStore | kVarFastDiv;
+    constexpr unsigned kVar = with_block<512>(kVarNT | kVarLdsStore | kVarFastDiv);
     float4* const slots = wave_slots<kVar>();
     const RowSink<kVar, float> coef_sink{coef, g.width, slots};
     float acc_f = 0.0f;
@@ -76,7 +76,7 @@ __global__ __launch_bounds__(512, 2) void roundtrip_pk_kernel(const uint8_t* __r
     }
     const uint32_t lane = threadIdx.x & 63u;
 
-    walk_sets<kVar>(img, g, slots, [&](const RawTile<uint8_t>& raw, const TilePos& p, uint32_t ok, uint64_t seg) {
+    walk_sets<kVar>(img, g, [&](const RawTile<uint8_t>& raw, const TilePos& p, uint32_t ok, uint64_t seg) {
         if constexpr (kStats) unroll<8>([&](auto i) { stash[i * 64u + lane] = raw.r[i]; });
         float xs[8][8];
         raw.to_float(xs, 0.0f);

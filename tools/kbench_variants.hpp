@@ -24,6 +24,21 @@
 namespace hpdct {
 namespace ab {
 
+// Resident waves per CU the persistent kernels are sized for (4 waves/SIMD at
+// <= 128 VGPRs); 256 CUs on MI355X.  The grid never exceeds the set count.
+constexpr uint32_t kPersistWavesPerCU = 16;
+// workgroups of a tile-per-lane launch; persist: at most the resident waves of cus CUs
+inline dim3 grid_for(const TileGrid& g, bool persist, uint32_t cus, uint32_t block = kBlockThreads) {
+    const uint32_t sets = (g.ntiles + 63u) / 64u;
+    const uint32_t waves_per_block = block / 64u;
+    uint32_t blocks = (sets + waves_per_block - 1) / waves_per_block;
+    if (persist) {
+        const uint32_t cap = cus * kPersistWavesPerCU / waves_per_block;
+        if (blocks > cap) blocks = cap;
+    }
+    return dim3(blocks);
+}
+
 // Compile-time kernel variants (bit flags).
 enum : unsigned {
     kVarFastDiv = 1u,  // quotient by  q0=c*r; e=fma(-q0,Q,c); q=fma(e,r,q0)  (r = RN(1/Q)).  Gives the same
