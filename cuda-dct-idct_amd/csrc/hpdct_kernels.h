@@ -51,6 +51,12 @@ enum : unsigned {
                              // four 256-B runs (a whole row of the wave's 8 tiles each) instead of
                              // 16-B pieces at a 32-B stride
 };
+// the block-format kernels' own variant bit (hpdct_blocks.hpp)
+enum : unsigned {
+    kBlkStaged = 1u << 21,  // forward: a whole 64-tile set's 8 KiB of int16 blocks re-staged through LDS, so
+                            // each store instruction writes 1 KiB contiguous instead of 16 B per lane at a
+                            // 128-B stride (tools/kb_blocks A/B)
+};
 // Bits only the product kernels give a meaning to: the tools' A/B variant
 // bits must stay clear of them (static_assert in tools/kbench_variants.hpp).
 constexpr unsigned kProductOnlyVarBits = kVarFastDivChecked | kVarJpegQ;
@@ -167,6 +173,17 @@ hipError_t launch_fdct_frames(const FrameTable<TOut>& ft, int n, const TileGrid&
 // the duo forward over such a list (fp32 out; c.grid_y frames)
 hipError_t launch_fdct_duo_u8_frames(const FrameTable<float>& ft, const TileGrid& g, const QParams& qp,
                                      const policy::Choice& c, hipStream_t s);
+
+// JPEG-style int16 coefficient blocks (hpdct_blocks.hpp): block t = tile t in
+// row-major tile order, 64 int16 each, zig-zag or (natural) row-major inside.
+// Tile-per-lane kernels only, as policy::forward_blocks / inverse_blocks choose.
+// Forward: uint8 frame, built-in T, level shift 128, quantised with qp (qmode
+// as launch_fdct; the caller proved |q| <= 32767).
+hipError_t launch_fdct_blocks(const uint8_t* img, int16_t* blocks, const TileGrid& g, const QParams& qp, int qmode,
+                              bool natural, hipStream_t s);
+// Inverse: blocks -> fp32 pixels (R + 128, no clamp; out_f32) or uint8 (clamp + truncate)
+hipError_t launch_idct_blocks(const int16_t* blocks, void* out, bool out_f32, const TileGrid& g, const Mat64& q,
+                              bool natural, hipStream_t s);
 
 hipError_t launch_fill_hash(uint8_t* out, uint64_t n, uint64_t seed, uint64_t first, hipStream_t s);
 

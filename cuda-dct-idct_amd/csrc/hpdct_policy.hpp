@@ -13,7 +13,8 @@ namespace policy {
 
 // kTile: fdct / idct / fdct_frames_kernel; kDuo: the fp32 duo kernels;
 // kDuoFwdU8: fdct_duo_u8(_frames)_kernel; kRt*: the round-trip kernels
-enum class Family { kTile, kOctet, kDuo, kDuoFwdU8, kRowFirstDuo, kRtDuo, kRtTile };
+// kBlocks: fdct_blocks_kernel / idct_blocks_kernel (hpdct_blocks.hpp)
+enum class Family { kTile, kOctet, kDuo, kDuoFwdU8, kRowFirstDuo, kRtDuo, kRtTile, kBlocks };
 enum class Elem { kU8, kI8, kF32 };
 
 // var: the kernel's kVar; kDuoFwdU8 and kRt* carry their quotient and straddle bits there
@@ -270,6 +271,27 @@ inline Choice inverse(const Call& c) {
     const bool straddle = c.in == Elem::kI8 && c.out == Elem::kF32 && c.builtin_t && c.g.tiles_x % 64u != 0u;
     return uncapped(Family::kTile, prod_var(c.out) | (f32 ? wb : 0u) | (straddle ? kVarStraddle : 0u),
                     tile_waves(c.g));
+}
+
+// JPEG-style int16 blocks (hpdct_blocks.hpp): the tile-per-lane mapping only
+// (c.mapping is not read), the int8 kernels' shape: 256-thread workgroups,
+// non-temporal stores, no residency cap.  Forward store path: the LDS-staged
+// 1 KiB runs (kBlkStaged) against eight 16-B stores per lane at a 128-B stride,
+// tools/kb_blocks A/B (DESIGN.md "int16 coefficient blocks").
+constexpr unsigned kBlocksFwdStore = kBlkStaged;
+constexpr unsigned kBlocksFwdVar = with_block<256>(kVarNT) | kBlocksFwdStore;
+// launch_fdct_blocks: uint8 in, built-in T, level shift 128; c.g and c.qmode
+inline Choice forward_blocks(const Call& c) {
+    return uncapped(Family::kBlocks, kBlocksFwdVar | quot_bits(c.qmode), tile_waves(c.g));
+}
+// launch_idct_blocks: c.g and c.out (fp32 or uint8 pixels); fp32 rows
+// LDS-re-staged, two-run staged stores for straddling sets (kVarStraddle)
+constexpr unsigned blocks_inv_var(Elem out) {
+    return with_block<256>(kVarNT) | (out == Elem::kF32 ? kVarLdsStore : 0u);
+}
+inline Choice inverse_blocks(const Call& c) {
+    const bool straddle = c.out == Elem::kF32 && c.g.tiles_x % 64u != 0u;
+    return uncapped(Family::kBlocks, blocks_inv_var(c.out) | (straddle ? kVarStraddle : 0u), tile_waves(c.g));
 }
 
 // launch_roundtrip.  The two-lanes-per-tile round trip (hpdct_rt_duo.hpp) for

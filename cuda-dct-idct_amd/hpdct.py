@@ -31,6 +31,8 @@ FLAG_WRITEBACK_SHIFT = 0x2
 FLAG_NO_SHIFT = 0x4
 FLAG_ROW_FIRST = 0x8
 FLAG_WRITEBACK_DEQUANT = 0x10
+BLOCKS_NATURAL = 0x1
+BLOCK_ORDERS = {"zigzag": 0, "natural": BLOCKS_NATURAL}
 
 STATUS = {
     0: "HPDCT_SUCCESS",
@@ -53,6 +55,7 @@ C_SYMBOLS = [
     "hpdct_roundtrip_u8", "hpdct_roundtrip_u8_accumulate", "hpdct_forward_frames",
     "hpdct_stream_create", "hpdct_stream_run", "hpdct_stream_destroy", "hpdct_decode_i8_f32",
     "hpdct_roundtrip_release_sums", "hpdct_floor_probe", "hpdct_copy_ceiling",
+    "hpdct_forward_blocks", "hpdct_inverse_blocks", "hpdct_zigzag_order",
 ]
 MAPPINGS = {"auto": 0, "tile": 1, "octet": 2, "duo": 3}
 BASELINES = {"reference_3pass": 0, "fastappr_3pass": 1}
@@ -111,6 +114,12 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.hpdct_copy_ceiling.restype = ctypes.c_int
     lib.hpdct_roundtrip_release_sums.argtypes = [vp]
     lib.hpdct_roundtrip_release_sums.restype = ctypes.c_int
+    lib.hpdct_forward_blocks.argtypes = [vp, vp, i64, i64, ctypes.c_uint, vp]
+    lib.hpdct_forward_blocks.restype = ctypes.c_int
+    lib.hpdct_inverse_blocks.argtypes = [vp, vp, ctypes.c_int, i64, i64, ctypes.c_uint, vp]
+    lib.hpdct_inverse_blocks.restype = ctypes.c_int
+    lib.hpdct_zigzag_order.argtypes = [vp]
+    lib.hpdct_zigzag_order.restype = None
     lib.hpdct_status_string.restype = ctypes.c_char_p
     lib.hpdct_status_string.argtypes = [ctypes.c_int]
     lib.hpdct_last_error_string.restype = ctypes.c_char_p
@@ -358,6 +367,111 @@ def bind(direction: str, src, dst, *, transform=None, quantise=True, level_shift
         (FLAG_WRITEBACK_DEQUANT if writeback_dequant else 0)
     args = (ctypes.c_void_p(src.data_ptr()), _dtype_code(src), ctypes.c_void_p(dst.data_ptr()), _dtype_code(dst),
             h, w, _transform_ptr(transform, src.device), flags, _stream_ptr(stream))
+
+    def call():
+        st = fn(*args)
+        if st:
+            _check(st)
+    return call
+
+
+# ---------------------------------------------------------------------------
+# JPEG-style int16 coefficient blocks (hpdct_forward_blocks / _inverse_blocks)
+# ---------------------------------------------------------------------------
+def zigzag_order() -> np.ndarray:
+    """The JPEG zig-zag scan (hpdct_zigzag_order): element n is the row-major
+    index 8*v + u of the n-th coefficient of a block."""
+    z = np.empty(64, np.uint8)
+    load_library().hpdct_zigzag_order(z.ctypes.data)
+    return z
+
+
+def _block_flags(order: str) -> int:
+    if order not in BLOCK_ORDERS:
+        raise ValueError(f"order must be one of {sorted(BLOCK_ORDERS)}")
+    return BLOCK_ORDERS[order]
+
+
+def _frame_hw(h: int, w: int):
+    if h <= 0 or w <= 0 or h % 8 or w % 8:
+        raise HpdctError(1, f"height and width must be positive multiples of 8 (got {h}x{w})")
+    return h, w
+
+
+def _block_planes(direction: str, src, dst, height, width):
+    """Buffer checks of one block launch (the C-ABI sees raw pointers only);
+    returns (image, blocks, h, w).  fwd: src the uint8 frame, dst the int16
+    blocks; inv: src the blocks, dst the fp32 or uint8 pixels."""
+    torch = _torch()
+    if direction == "fwd":
+        _device_plane(src, "image", None, 0, (torch.uint8,))
+        h, w = _frame_hw(*_hw(src, height, width))
+        _device_plane(dst, "out", src.device, h * w, (torch.int16,))
+        return src, dst, h, w
+    _device_plane(src, "blocks", None, 0, (torch.int16,))
+    if height is None or width is None:
+        if src.dim() != 3 or src.shape[-1] != 64:
+            raise HpdctError(1, "pass height and width for blocks that are not (H/8, W/8, 64)")
+        height, width = 8 * src.shape[0], 8 * src.shape[1]
+    h, w = _frame_hw(int(height), int(width))
+    if src.numel() < h * w:
+        raise HpdctError(1, f"blocks hold {src.numel()} elements, a {h}x{w} frame needs {h * w}")
+    _device_plane(dst, "out", src.device, h * w, (torch.float32, torch.uint8))
+    return dst, src, h, w
+
+
+def forward_blocks(image, out=None, *, order: str = "zigzag", height=None, width=None, stream=None):
+    """uint8 frame -> JPEG-style int16 blocks, shape (H/8, W/8, 64): block
+    [by, bx] holds tile (by, bx)'s quantised coefficients in zig-zag (or
+    "natural", row-major) order.  The values of forward() cast to int16.  A
+    stack of frames is one (F*H) x W image: each frame's blocks stay together."""
+    torch = _torch()
+    flags = _block_flags(order)
+    _device_plane(image, "image", None, 0, (torch.uint8,))
+    h, w = _frame_hw(*_hw(image, height, width))
+    if out is None:
+        out = torch.empty((h // 8, w // 8, 64), dtype=torch.int16, device=image.device)
+    _block_planes("fwd", image, out, h, w)
+    _check(load_library().hpdct_forward_blocks(ctypes.c_void_p(image.data_ptr()), ctypes.c_void_p(out.data_ptr()),
+                                               h, w, flags, _stream_ptr(stream)))
+    return out
+
+
+def inverse_blocks(blocks, out=None, *, out_dtype=None, order: str = "zigzag", height=None, width=None,
+                   stream=None):
+    """int16 blocks -> pixels: float32 (R + 128, no clamp) or uint8 (clamp +
+    truncate), as inverse() on the spatial plane of the same values.  height
+    and width come from a (H/8, W/8, 64) tensor when not given."""
+    torch = _torch()
+    flags = _block_flags(order)
+    _device_plane(blocks, "blocks", None, 0, (torch.int16,))
+    if out is None:
+        if height is None or width is None:
+            if blocks.dim() != 3 or blocks.shape[-1] != 64:
+                raise HpdctError(1, "pass height and width for blocks that are not (H/8, W/8, 64)")
+            height, width = 8 * blocks.shape[0], 8 * blocks.shape[1]
+        h, w = _frame_hw(int(height), int(width))
+        out = torch.empty((h, w), dtype=out_dtype or torch.float32, device=blocks.device)
+    _, _, h, w = _block_planes("inv", blocks, out, height, width)
+    _check(load_library().hpdct_inverse_blocks(ctypes.c_void_p(blocks.data_ptr()), ctypes.c_void_p(out.data_ptr()),
+                                               _dtype_code(out), h, w, flags, _stream_ptr(stream)))
+    return out
+
+
+def bind_blocks(direction: str, src, dst, *, order: str = "zigzag", height=None, width=None, stream=None):
+    """Pre-resolved forward_blocks ("fwd": uint8 frame -> int16 blocks) or
+    inverse_blocks ("inv": blocks -> fp32 / uint8 pixels) launch: a
+    zero-argument callable like bind(), for timing."""
+    if direction not in ("fwd", "inv"):
+        raise ValueError('direction must be "fwd" or "inv"')
+    flags = _block_flags(order)
+    image, blocks, h, w = _block_planes(direction, src, dst, height, width)
+    lib = load_library()
+    ip, bp = ctypes.c_void_p(image.data_ptr()), ctypes.c_void_p(blocks.data_ptr())
+    if direction == "fwd":
+        fn, args = lib.hpdct_forward_blocks, (ip, bp, h, w, flags, _stream_ptr(stream))
+    else:
+        fn, args = lib.hpdct_inverse_blocks, (bp, ip, _dtype_code(image), h, w, flags, _stream_ptr(stream))
 
     def call():
         st = fn(*args)

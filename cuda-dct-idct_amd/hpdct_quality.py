@@ -27,11 +27,10 @@ import numpy as np
 
 import hpdct
 
-# JPEG zig-zag scan: ZIGZAG[n] = row-major index (8*v + u) of the n-th coefficient
-ZIGZAG = [0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5,
-          12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
-          35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51,
-          58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63]
+# JPEG zig-zag scan: ZIGZAG[n] = row-major index (8*v + u) of the n-th
+# coefficient; the library's one table (hpdct_zigzag_order, the order of
+# forward_blocks)
+ZIGZAG = [int(i) for i in hpdct.zigzag_order()]
 
 
 def retain_mask(k: int) -> np.ndarray:

@@ -250,6 +250,39 @@ hpdct_status hpdct_fill_hash_u8(uint8_t* d_out, int64_t n, uint64_t seed, int64_
  * `stream`.  No reference counterpart (the reference has no int8 format). */
 hpdct_status hpdct_decode_i8_f32(const int8_t* d_q, float* d_out, int64_t n, void* stream);
 
+/* JPEG-style coefficient blocks (no reference counterpart: the reference keeps
+ * its coefficients in the spatial layout).  What an entropy coder or libjpeg's
+ * jpeg_write_coefficients takes: one block of 64 int16 per 8x8 tile, block
+ * after block.
+ *   layout  block t = tile t in row-major tile order, t = by * (width/8) + bx,
+ *           at d_blocks + 64 * t; element n of a block = the quantised
+ *           coefficient at row-major position zigzag[n] (hpdct_zigzag_order),
+ *           or at n with HPDCT_BLOCKS_NATURAL (row-major (v,u): what libjpeg's
+ *           coefficient arrays hold).  A stack of F frames, (F*height) x width,
+ *           gives each frame's blocks contiguously, frame after frame.
+ *   forward uint8 frame -> blocks.  Built-in T, the library Q, level shift 128.
+ *           The values equal hpdct_forward U8 -> F32 on the same frame, cast
+ *           to int16 (a -0.0 becomes 0); the quotient is chosen as
+ *           hpdct_forward chooses it.  int16 holds every |q| <= 32767, i.e.
+ *           every table with |Q| >= 1/31 everywhere (|C| <= 1024 with the
+ *           built-in T), so also the tables HPDCT_I8 refuses (any DC entry
+ *           below ~8.06, e.g. libjpeg's quality-75 luminance table); a table
+ *           that can exceed it returns HPDCT_ERROR_RANGE.
+ *   inverse blocks -> out_type HPDCT_F32 (R+128, no clamp) or HPDCT_U8 (clamp
+ *           + truncate) pixels: equal, bit for bit, to hpdct_inverse F32 ->
+ *           out_type on the spatial fp32 plane that holds (float)block value.
+ *   d_blocks 16-byte aligned, height*width int16; d_image 8-byte (HPDCT_U8) or
+ *   16-byte (HPDCT_F32) aligned; the two must not overlap.  flags:
+ *   HPDCT_BLOCKS_NATURAL or 0, anything else HPDCT_ERROR_UNSUPPORTED.
+ *   Asynchronous on `stream`.  hpdct_set_mapping does not affect these calls:
+ *   only the one-lane-per-tile mapping exists for them. */
+#define HPDCT_BLOCKS_NATURAL 0x1u /* within a block: row-major (v,u) order instead of zig-zag */
+hpdct_status hpdct_forward_blocks(const uint8_t* d_image, int16_t* d_blocks, int64_t height, int64_t width,
+                                  unsigned flags, void* stream);
+hpdct_status hpdct_inverse_blocks(const int16_t* d_blocks, void* d_image, hpdct_dtype out_type, int64_t height,
+                                  int64_t width, unsigned flags, void* stream);
+void hpdct_zigzag_order(uint8_t* z64); /* z64[n] = 8*v+u of the n-th zig-zag coefficient (host memory) */
+
 /* Work mapping of the kernels (new; the reference has one fixed decomposition
  * per program).  Output is bit-identical in every mapping; only speed differs.
  *   AUTO   per frame: eight lanes per 8x8 tile ("octet") for frames below

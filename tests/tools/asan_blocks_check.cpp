@@ -1,0 +1,74 @@
+// asan_blocks_check.cpp -- drives the validation paths of hpdct_forward_blocks /
+// hpdct_inverse_blocks and hpdct_zigzag_order under ASan + UBSan, CPU only: a
+// stand-alone program linked with the sanitised hpdct_api.cpp (g++) and the
+// library's kernel objects, as tests/tools/asan.mk links asan_host_check.  No
+// kernel is launched: every call here fails its checks (or touches host
+// memory only).  Built and run by tests/test_blocks_host.py.
+#include <cstdint>
+#include <cstdio>
+#include <cstring>
+#include <memory>
+
+#include "hpdct.h"
+
+namespace {
+int g_bad = 0;
+void expect(const char* what, int got, int want, const char* text = nullptr) {
+    const bool ok = got == want && (!text || std::strstr(hpdct_last_error_string(), text));
+    if (!ok) {
+        ++g_bad;
+        std::printf("MISMATCH %s: status %d (expected %d), last error \"%s\"\n", what, got, want,
+                    hpdct_last_error_string());
+    }
+}
+}  // namespace
+
+int main() {
+    // never dereferenced: validation fails first
+    const auto A = reinterpret_cast<uint8_t*>(uintptr_t(1) << 20);
+    const auto B = reinterpret_cast<int16_t*>(uintptr_t(1) << 30);
+    auto at = [](auto* p, intptr_t bytes) {
+        return reinterpret_cast<decltype(p)>(reinterpret_cast<uintptr_t>(p) + bytes);
+    };
+    expect("fwd null image", hpdct_forward_blocks(nullptr, B, 8, 8, 0, nullptr), 1);
+    expect("fwd null blocks", hpdct_forward_blocks(A, nullptr, 8, 8, 0, nullptr), 1);
+    expect("fwd 12x8", hpdct_forward_blocks(A, B, 12, 8, 0, nullptr), 1, "multiples of 8");
+    expect("fwd 8x20", hpdct_forward_blocks(A, B, 8, 20, 0, nullptr), 1, "multiples of 8");
+    expect("fwd huge", hpdct_forward_blocks(A, B, int64_t(1) << 23, int64_t(1) << 23, 0, nullptr), 1, "too large");
+    expect("fwd blocks + 8", hpdct_forward_blocks(A, at(B, 8), 8, 8, 0, nullptr), 1, "aligned");
+    expect("fwd overlap", hpdct_forward_blocks(A, reinterpret_cast<int16_t*>(at(A, 32)), 8, 8, 0, nullptr), 1,
+           "overlap");
+    expect("fwd flag 0x80", hpdct_forward_blocks(A, B, 8, 8, 0x80u, nullptr), 2);
+    expect("inv null", hpdct_inverse_blocks(nullptr, A, HPDCT_U8, 8, 8, 0, nullptr), 1);
+    expect("inv 8x20", hpdct_inverse_blocks(B, A, HPDCT_F32, 8, 20, 0, nullptr), 1, "multiples of 8");
+    expect("inv I8 out", hpdct_inverse_blocks(B, A, HPDCT_I8, 8, 8, 0, nullptr), 2);
+    expect("inv fp32 pixels + 8", hpdct_inverse_blocks(B, at(A, 8), HPDCT_F32, 8, 8, 0, nullptr), 1, "aligned");
+    expect("inv overlap", hpdct_inverse_blocks(B, at(reinterpret_cast<uint8_t*>(B), 64), HPDCT_U8, 8, 8, 0, nullptr), 1,
+           "overlap");
+    expect("inv flag 0x80", hpdct_inverse_blocks(B, A, HPDCT_U8, 8, 8, HPDCT_BLOCKS_NATURAL | 0x80u, nullptr), 2);
+
+    // the range rule: 1/64 everywhere can give |q| = 65536
+    float q[64];
+    for (float& v : q) v = 1.0f / 64.0f;
+    expect("set 1/64 table", hpdct_set_quant_table(q), 0);
+    expect("fwd range", hpdct_forward_blocks(A, B, 8, 8, 0, nullptr), 3, "int16");
+    expect("restore table", hpdct_set_quant_table(nullptr), 0);
+
+    // exactly 64 bytes on the heap: a write past them is an ASan report
+    std::unique_ptr<uint8_t[]> z(new uint8_t[64]);
+    hpdct_zigzag_order(z.get());
+    hpdct_zigzag_order(nullptr);
+    bool seen[64] = {};
+    for (int n = 0; n < 64; ++n) {
+        if (z[n] >= 64 || seen[z[n]]) ++g_bad;
+        else seen[z[n]] = true;
+    }
+    if (z[0] != 0 || z[1] != 1 || z[2] != 8 || z[63] != 63) ++g_bad;
+
+    if (g_bad != 0) {
+        std::printf("asan_blocks_check: %d checks failed\n", g_bad);
+        return 1;
+    }
+    std::printf("asan_blocks_check: ok\n");
+    return 0;
+}
