@@ -57,6 +57,13 @@ enum : unsigned {
                             // each store instruction writes 1 KiB contiguous instead of 16 B per lane at a
                             // 128-B stride (tools/kb_blocks A/B)
 };
+// the colour kernels' own variant bits (hpdct_rgb.hpp; they also read kBlkStaged)
+enum : unsigned {
+    kRgb420 = 1u << 22,            // 4:2:0: one lane per 16x16 MCU (clear: 4:4:4, one lane per 8x8 pixel tile)
+    kRgbChromaFastDiv = 1u << 23,  // forward: the verified 3-op quotient for Cb and Cr (the chroma table's
+                                   // entries are all integers in 1..255); the luma quotient is in the
+                                   // kVarFastDiv / kVarJpegQ bits as everywhere
+};
 // Bits only the product kernels give a meaning to: the tools' A/B variant
 // bits must stay clear of them (static_assert in tools/kbench_variants.hpp).
 constexpr unsigned kProductOnlyVarBits = kVarFastDivChecked | kVarJpegQ;
@@ -184,6 +191,31 @@ hipError_t launch_fdct_blocks(const uint8_t* img, int16_t* blocks, const TileGri
 // Inverse: blocks -> fp32 pixels (R + 128, no clamp; out_f32) or uint8 (clamp + truncate)
 hipError_t launch_idct_blocks(const int16_t* blocks, void* out, bool out_f32, const TileGrid& g, const Mat64& q,
                               bool natural, hipStream_t s);
+
+// Colour frames (hpdct_rgb.hpp): interleaved uint8 RGB <-> three int16 block
+// arrays (Y, Cb, Cr), 4:4:4 or 4:2:0, one launch per direction.  A lane owns
+// one unit: an 8x8 pixel tile (4:4:4) or a 16x16 MCU (4:2:0), 64 units in
+// row-major unit order per wave.  nunits < 2^32.
+struct RgbGrid {
+    uint32_t nunits;
+    uint32_t units_x;  // units per row of units
+    uint64_t width;    // pixels per image row
+};
+// Forward: built-in T, level shift 128; Y quantised with ql, Cb and Cr with qc
+// (qmode_* as launch_fdct; the caller proved |q| <= 32767 for both tables).
+hipError_t launch_fdct_rgb(const uint8_t* rgb, int16_t* y, int16_t* cb, int16_t* cr, const RgbGrid& g, bool s420,
+                           const QParams& ql, const QParams& qc, int qmode_luma, int qmode_chroma, bool natural,
+                           hipStream_t s);
+// Inverse: blocks -> uint8 components (clamp + truncate) -> RGB
+hipError_t launch_idct_rgb(const int16_t* y, const int16_t* cb, const int16_t* cr, uint8_t* rgb, const RgbGrid& g,
+                           bool s420, const Mat64& ql, const Mat64& qc, bool natural, hipStream_t s);
+// the per-subsampling units of the forward (hpdct_rgb_fwd420.hip / hpdct_rgb_fwd444.hip), as c chose
+hipError_t launch_fdct_rgb_420(const uint8_t* rgb, int16_t* y, int16_t* cb, int16_t* cr, const RgbGrid& g,
+                               const QParams& ql, const QParams& qc, bool natural, const policy::Choice& c,
+                               hipStream_t s);
+hipError_t launch_fdct_rgb_444(const uint8_t* rgb, int16_t* y, int16_t* cb, int16_t* cr, const RgbGrid& g,
+                               const QParams& ql, const QParams& qc, bool natural, const policy::Choice& c,
+                               hipStream_t s);
 
 hipError_t launch_fill_hash(uint8_t* out, uint64_t n, uint64_t seed, uint64_t first, hipStream_t s);
 

@@ -14,7 +14,8 @@ namespace policy {
 // kTile: fdct / idct / fdct_frames_kernel; kDuo: the fp32 duo kernels;
 // kDuoFwdU8: fdct_duo_u8(_frames)_kernel; kRt*: the round-trip kernels
 // kBlocks: fdct_blocks_kernel / idct_blocks_kernel (hpdct_blocks.hpp)
-enum class Family { kTile, kOctet, kDuo, kDuoFwdU8, kRowFirstDuo, kRtDuo, kRtTile, kBlocks };
+// kRgb: fdct_rgb_kernel / idct_rgb_kernel (hpdct_rgb.hpp)
+enum class Family { kTile, kOctet, kDuo, kDuoFwdU8, kRowFirstDuo, kRtDuo, kRtTile, kBlocks, kRgb };
 enum class Elem { kU8, kI8, kF32 };
 
 // var: the kernel's kVar; kDuoFwdU8 and kRt* carry their quotient and straddle bits there
@@ -292,6 +293,33 @@ constexpr unsigned blocks_inv_var(Elem out) {
 inline Choice inverse_blocks(const Call& c) {
     const bool straddle = c.out == Elem::kF32 && c.g.tiles_x % 64u != 0u;
     return uncapped(Family::kBlocks, blocks_inv_var(c.out) | (straddle ? kVarStraddle : 0u), tile_waves(c.g));
+}
+
+// Colour frames (hpdct_rgb.hpp): one lane per unit (an 8x8 pixel tile for
+// 4:4:4, a 16x16 MCU for 4:2:0), 64 units per wave, 256-thread workgroups, no
+// residency cap (their LDS image already holds a CU to 5 (4:4:4) or 2 (4:2:0)
+// workgroups); hpdct_set_mapping is not read.
+struct RgbCall {
+    uint32_t units = 0;
+    bool s420 = false;
+    int qmode_luma = 0, qmode_chroma = 0;  // forward only; chroma 0 or 1
+};
+constexpr uint32_t rgb_waves(const RgbCall& c) { return c.units / 64u + (c.units % 64u != 0u); }
+// Forward: block stores LDS-staged into 1 KiB runs (kBlkStaged, as the plane
+// kernel's A/B chose), non-temporal.  Quotient pairs (luma, chroma) the launchers
+// hold: (JPEG forms, 3-op), (3-op, 3-op), and IEEE division for both when
+// either table is not all integers in 1..255 (every form gives the same result).
+constexpr unsigned kRgbFwdVar = with_block<256>(kVarNT) | kBlkStaged;
+inline Choice forward_rgb(const RgbCall& c) {
+    const bool fast = c.qmode_luma != 0 && c.qmode_chroma != 0;
+    return uncapped(Family::kRgb,
+                    kRgbFwdVar | (c.s420 ? kRgb420 : 0u) | (fast ? quot_bits(c.qmode_luma) | kRgbChromaFastDiv : 0u),
+                    rgb_waves(c));
+}
+// Inverse: per-lane loads of whole blocks, plain per-lane RGB row stores
+constexpr unsigned kRgbInvVar = with_block<256>(0u);
+inline Choice inverse_rgb(const RgbCall& c) {
+    return uncapped(Family::kRgb, kRgbInvVar | (c.s420 ? kRgb420 : 0u), rgb_waves(c));
 }
 
 // launch_roundtrip.  The two-lanes-per-tile round trip (hpdct_rt_duo.hpp) for

@@ -56,6 +56,7 @@ C_SYMBOLS = [
     "hpdct_stream_create", "hpdct_stream_run", "hpdct_stream_destroy", "hpdct_decode_i8_f32",
     "hpdct_roundtrip_release_sums", "hpdct_floor_probe", "hpdct_copy_ceiling",
     "hpdct_forward_blocks", "hpdct_inverse_blocks", "hpdct_zigzag_order",
+    "hpdct_default_chroma_quant_table", "hpdct_forward_rgb_blocks", "hpdct_inverse_rgb_blocks",
 ]
 MAPPINGS = {"auto": 0, "tile": 1, "octet": 2, "duo": 3}
 BASELINES = {"reference_3pass": 0, "fastappr_3pass": 1}
@@ -120,6 +121,11 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.hpdct_inverse_blocks.restype = ctypes.c_int
     lib.hpdct_zigzag_order.argtypes = [vp]
     lib.hpdct_zigzag_order.restype = None
+    lib.hpdct_default_chroma_quant_table.argtypes = [vp]
+    lib.hpdct_default_chroma_quant_table.restype = None
+    for f in (lib.hpdct_forward_rgb_blocks, lib.hpdct_inverse_rgb_blocks):
+        f.argtypes = [vp, vp, vp, vp, i64, i64, ctypes.c_int, vp, vp, ctypes.c_uint, vp]
+        f.restype = ctypes.c_int
     lib.hpdct_status_string.restype = ctypes.c_char_p
     lib.hpdct_status_string.argtypes = [ctypes.c_int]
     lib.hpdct_last_error_string.restype = ctypes.c_char_p
@@ -478,6 +484,154 @@ def bind_blocks(direction: str, src, dst, *, order: str = "zigzag", height=None,
         if st:
             _check(st)
     return call
+
+
+# ---------------------------------------------------------------------------
+# Colour frames (hpdct_forward_rgb_blocks / hpdct_inverse_rgb_blocks)
+# ---------------------------------------------------------------------------
+SUBSAMPLINGS = {"444": 0, "420": 1}  # HPDCT_SUBSAMPLING_*
+
+
+def default_chroma_quant_table() -> np.ndarray:
+    """The JPEG Annex K chrominance table (hpdct_default_chroma_quant_table)."""
+    q = np.empty(64, np.float32)
+    load_library().hpdct_default_chroma_quant_table(q.ctypes.data)
+    return q.reshape(8, 8)
+
+
+def _subsampling(name) -> int:
+    if name not in SUBSAMPLINGS:
+        raise ValueError(f"subsampling must be one of {sorted(SUBSAMPLINGS)}")
+    return SUBSAMPLINGS[name]
+
+
+def _host_table(q):
+    """None, or the 64 floats of a per-call table as a contiguous host array
+    (the library reads it during the call)."""
+    if q is None:
+        return None
+    a = np.ascontiguousarray(np.asarray(q, dtype=np.float32).reshape(-1))
+    if a.size != 64:
+        raise HpdctError(1, f"a quant table holds 64 floats, not {a.size}")
+    return a
+
+
+def _rgb_hw(rgb, sub: int):
+    """(h, w) of an (..., H, W, 3) uint8 frame or stack, checked against the subsampling."""
+    if rgb.dim() < 3 or rgb.shape[-1] != 3:
+        raise HpdctError(1, "the RGB frame must be shaped (H, W, 3)")
+    w = int(rgb.shape[-2])
+    h = rgb.numel() // (3 * w) if w else 0
+    side = 16 if sub == 1 else 8
+    if h <= 0 or w <= 0 or h % side or w % side:
+        raise HpdctError(1, f"height and width must be positive multiples of {side} (got {h}x{w})")
+    return h, w
+
+
+def _rgb_planes(rgb, y, cb, cr, h: int, w: int, sub: int):
+    """Buffer checks of one colour launch, those of _block_planes: device,
+    dtype, contiguity, size and overlap of the RGB frame and the three block
+    arrays (the C-ABI sees raw pointers only)."""
+    torch = _torch()
+    _device_plane(rgb, "rgb", None, 3 * h * w, (torch.uint8,))
+    ch, cw = (h // 2, w // 2) if sub == 1 else (h, w)
+    for t, what, need in ((y, "y blocks", h * w), (cb, "cb blocks", ch * cw), (cr, "cr blocks", ch * cw)):
+        _device_plane(t, what, rgb.device, need, (torch.int16,))
+    spans = [(t.data_ptr(), t.data_ptr() + n, what) for t, n, what in
+             ((rgb, 3 * h * w, "rgb"), (y, 2 * h * w, "y"), (cb, 2 * ch * cw, "cb"), (cr, 2 * ch * cw, "cr"))]
+    for i in range(4):
+        for j in range(i + 1, 4):
+            if spans[i][0] < spans[j][1] and spans[j][0] < spans[i][1]:
+                raise HpdctError(1, f"the {spans[i][2]} and {spans[j][2]} buffers overlap")
+
+
+def _rgb_block_shapes(h: int, w: int, sub: int):
+    ch, cw = (h // 2, w // 2) if sub == 1 else (h, w)
+    return (h // 8, w // 8, 64), (ch // 8, cw // 8, 64)
+
+
+def _rgb_call(fn, ptrs, h, w, sub, ql, qc, flags, stream):
+    args = tuple(ctypes.c_void_p(p) for p in ptrs) + (
+        h, w, sub, None if ql is None else ql.ctypes.data, None if qc is None else qc.ctypes.data, flags,
+        _stream_ptr(stream))
+
+    def call():
+        st = fn(*args)
+        if st:
+            _check(st)
+    call.tables = (ql, qc)  # the host tables live as long as the callable
+    return call
+
+
+def forward_rgb_blocks(rgb, *, subsampling: str = "420", q_luma=None, q_chroma=None, order: str = "zigzag",
+                       out=None, stream=None):
+    """Interleaved uint8 RGB (H, W, 3) -> (y, cb, cr) int16 blocks in one launch:
+    y (H/8, W/8, 64), cb and cr (Hc/8, Wc/8, 64) with Hc x Wc = H x W ("444")
+    or H/2 x W/2 ("420").  q_luma None: the library table (set_quant_table);
+    q_chroma None: default_chroma_quant_table().  out: (y, cb, cr) to fill."""
+    torch = _torch()
+    sub, flags = _subsampling(subsampling), _block_flags(order)
+    _device_plane(rgb, "rgb", None, 0, (torch.uint8,))
+    h, w = _rgb_hw(rgb, sub)
+    if out is None:
+        ys, cs = _rgb_block_shapes(h, w, sub)
+        out = (torch.empty(ys, dtype=torch.int16, device=rgb.device),
+               torch.empty(cs, dtype=torch.int16, device=rgb.device),
+               torch.empty(cs, dtype=torch.int16, device=rgb.device))
+    y, cb, cr = out
+    _rgb_planes(rgb, y, cb, cr, h, w, sub)
+    _rgb_call(load_library().hpdct_forward_rgb_blocks, (rgb.data_ptr(), y.data_ptr(), cb.data_ptr(), cr.data_ptr()),
+              h, w, sub, _host_table(q_luma), _host_table(q_chroma), flags, stream)()
+    return y, cb, cr
+
+
+def _rgb_inverse_hw(y, sub: int, height, width):
+    if height is None or width is None:
+        if y.dim() != 3 or y.shape[-1] != 64:
+            raise HpdctError(1, "pass height and width for y blocks that are not (H/8, W/8, 64)")
+        height, width = 8 * y.shape[0], 8 * y.shape[1]
+    h, w = int(height), int(width)
+    side = 16 if sub == 1 else 8
+    if h <= 0 or w <= 0 or h % side or w % side:
+        raise HpdctError(1, f"height and width must be positive multiples of {side} (got {h}x{w})")
+    return h, w
+
+
+def inverse_rgb_blocks(y, cb, cr, *, subsampling: str, q_luma=None, q_chroma=None, order: str = "zigzag",
+                       out=None, height=None, width=None, stream=None):
+    """(y, cb, cr) int16 blocks -> interleaved uint8 RGB (H, W, 3) in one launch;
+    H and W come from a (H/8, W/8, 64) y tensor when not given."""
+    torch = _torch()
+    sub, flags = _subsampling(subsampling), _block_flags(order)
+    _device_plane(y, "y blocks", None, 0, (torch.int16,))
+    h, w = _rgb_inverse_hw(y, sub, height, width)
+    if out is None:
+        out = torch.empty((h, w, 3), dtype=torch.uint8, device=y.device)
+    _device_plane(out, "rgb", y.device, 3 * h * w, (torch.uint8,))
+    _rgb_planes(out, y, cb, cr, h, w, sub)
+    _rgb_call(load_library().hpdct_inverse_rgb_blocks, (y.data_ptr(), cb.data_ptr(), cr.data_ptr(), out.data_ptr()),
+              h, w, sub, _host_table(q_luma), _host_table(q_chroma), flags, stream)()
+    return out
+
+
+def bind_rgb_blocks(direction: str, rgb, y, cb, cr, *, subsampling: str = "420", q_luma=None, q_chroma=None,
+                    order: str = "zigzag", stream=None):
+    """Pre-resolved forward_rgb_blocks ("fwd") or inverse_rgb_blocks ("inv")
+    launch on the given buffers: a zero-argument callable like bind_blocks(),
+    for timing."""
+    if direction not in ("fwd", "inv"):
+        raise ValueError('direction must be "fwd" or "inv"')
+    torch = _torch()
+    sub, flags = _subsampling(subsampling), _block_flags(order)
+    _device_plane(rgb, "rgb", None, 0, (torch.uint8,))
+    h, w = _rgb_hw(rgb, sub)
+    _rgb_planes(rgb, y, cb, cr, h, w, sub)
+    lib = load_library()
+    if direction == "fwd":
+        fn, ptrs = lib.hpdct_forward_rgb_blocks, (rgb.data_ptr(), y.data_ptr(), cb.data_ptr(), cr.data_ptr())
+    else:
+        fn, ptrs = lib.hpdct_inverse_rgb_blocks, (y.data_ptr(), cb.data_ptr(), cr.data_ptr(), rgb.data_ptr())
+    return _rgb_call(fn, ptrs, h, w, sub, _host_table(q_luma), _host_table(q_chroma), flags, stream)
 
 
 SSE_F32_UNIT = 1.0 / 65536.0  # HPDCT_SSE_F32_UNIT

@@ -283,6 +283,66 @@ hpdct_status hpdct_inverse_blocks(const int16_t* d_blocks, void* d_image, hpdct_
                                   int64_t width, unsigned flags, void* stream);
 void hpdct_zigzag_order(uint8_t* z64); /* z64[n] = 8*v+u of the n-th zig-zag coefficient (host memory) */
 
+/* Colour frames: interleaved uint8 RGB <-> three arrays of int16 blocks (Y, Cb,
+ * Cr), 4:4:4 or 4:2:0, one kernel launch per direction (no reference
+ * counterpart: the reference is grey-scale).  Everything is integer arithmetic
+ * around the block transform above, so every result is exact; these formulas
+ * are the specification.
+ *   input   d_rgb: height rows of width pixels, dense: the row pitch is
+ *           3*width bytes and byte 3*x + c of a row is channel c (R, G, B) of
+ *           pixel x.  HPDCT_SUBSAMPLING_444: height and width positive
+ *           multiples of 8; HPDCT_SUBSAMPLING_420: of 16.  A stack of F frames
+ *           is the one image (F*height) x width.  The tile-count limit is
+ *           hpdct_forward_blocks' ((height/8)*(width/8) < 2^32).
+ *   convert per pixel, in int32 (every result is 0..255 without a clamp):
+ *             Y  = ( 19595*R + 38470*G +  7471*B + 32768) >> 16
+ *             Cb = (-11059*R - 21709*G + 32768*B + (128<<16) + 32767) >> 16
+ *             Cr = ( 32768*R - 27439*G -  5329*B + (128<<16) + 32767) >> 16
+ *   4:2:0   each chroma sample is (a + b + c + d + 2) >> 2 over the 2x2 quad of
+ *           the converted per-pixel Cb (Cr) values: convert, then average.
+ *   forward each component plane (Y: height x width; Cb, Cr: the same for
+ *           4:4:4, height/2 x width/2 for 4:2:0) goes through exactly
+ *           hpdct_forward_blocks' arithmetic: built-in T, level shift 128, the
+ *           quotient, the cast to int16 (-0.0 becomes 0).  Y is quantised with
+ *           the luma table, Cb and Cr with the chroma table.  d_y, d_cb, d_cr
+ *           are three separate block arrays, each laid out as
+ *           hpdct_forward_blocks lays out that plane (block t = tile t of the
+ *           component plane in row-major tile order; zig-zag inside, or
+ *           row-major with HPDCT_BLOCKS_NATURAL): d_y is bit for bit what
+ *           hpdct_forward_blocks writes for the Y plane under the luma table,
+ *           and each array can go straight into hpdct_inverse_blocks.
+ *   tables  q_luma64, q_chroma64: HOST pointers to 64 floats, read during the
+ *           call and passed to the kernel with its arguments: no process-wide
+ *           state, so calls with different tables may run on different streams
+ *           at once.  q_luma64 NULL: the library-owned table
+ *           (hpdct_set_quant_table).  q_chroma64 NULL: the JPEG Annex K
+ *           chrominance table (hpdct_default_chroma_quant_table).  Entries
+ *           must be finite and non-zero (HPDCT_ERROR_INVALID_VALUE); a table
+ *           that can give |q| > 32767 returns HPDCT_ERROR_RANGE.  The result
+ *           does not depend on which quotient form the library picks.
+ *   inverse each component's blocks through hpdct_inverse_blocks' arithmetic to
+ *           uint8 (clamp + truncate): Y, Cb, Cr.  4:2:0 chroma is replicated:
+ *           chroma sample (i, j) serves pixels (2i..2i+1, 2j..2j+1).  Then, in
+ *           int32 with arithmetic (flooring) right shifts,
+ *             R = clamp255(Y + (( 91881*(Cr-128) + 32768) >> 16))
+ *             G = clamp255(Y + ((-22554*(Cb-128) - 46802*(Cr-128) + 32768) >> 16))
+ *             B = clamp255(Y + ((116130*(Cb-128) + 32768) >> 16))
+ *           written as interleaved uint8 RGB in the input layout.  Without
+ *           quantisation loss the pair is the identity to within +-1 a channel.
+ *   All four device pointers 16-byte aligned; no buffer may overlap another.
+ *   flags: HPDCT_BLOCKS_NATURAL or 0, anything else HPDCT_ERROR_UNSUPPORTED; an
+ *   unknown subsampling HPDCT_ERROR_INVALID_VALUE.  Asynchronous on `stream`;
+ *   every argument is checked before any device call.  hpdct_set_mapping does
+ *   not affect these calls. */
+typedef enum hpdct_subsampling { HPDCT_SUBSAMPLING_444 = 0, HPDCT_SUBSAMPLING_420 = 1 } hpdct_subsampling;
+void hpdct_default_chroma_quant_table(float* q64); /* 64 floats, row-major (host memory) */
+hpdct_status hpdct_forward_rgb_blocks(const uint8_t* d_rgb, int16_t* d_y, int16_t* d_cb, int16_t* d_cr,
+                                      int64_t height, int64_t width, hpdct_subsampling sub,
+                                      const float* q_luma64, const float* q_chroma64, unsigned flags, void* stream);
+hpdct_status hpdct_inverse_rgb_blocks(const int16_t* d_y, const int16_t* d_cb, const int16_t* d_cr, uint8_t* d_rgb,
+                                      int64_t height, int64_t width, hpdct_subsampling sub,
+                                      const float* q_luma64, const float* q_chroma64, unsigned flags, void* stream);
+
 /* Work mapping of the kernels (new; the reference has one fixed decomposition
  * per program).  Output is bit-identical in every mapping; only speed differs.
  *   AUTO   per frame: eight lanes per 8x8 tile ("octet") for frames below
