@@ -63,6 +63,9 @@ enum : unsigned {
     kRgbChromaFastDiv = 1u << 23,  // forward: the verified 3-op quotient for Cb and Cr (the chroma table's
                                    // entries are all integers in 1..255); the luma quotient is in the
                                    // kVarFastDiv / kVarJpegQ bits as everywhere
+    kRgbClip = 1u << 24,           // the general instantiation: a frame that is not whole units (edge-replicated
+                                   // on the way in, cropped on the way out) or whose base or row pitch is not
+                                   // 8-byte aligned; clear: whole units, 8-byte loads and stores everywhere
 };
 // Bits only the product kernels give a meaning to: the tools' A/B variant
 // bits must stay clear of them (static_assert in tools/kbench_variants.hpp).
@@ -195,12 +198,22 @@ hipError_t launch_idct_blocks(const int16_t* blocks, void* out, bool out_f32, co
 // Colour frames (hpdct_rgb.hpp): interleaved uint8 RGB <-> three int16 block
 // arrays (Y, Cb, Cr), 4:4:4 or 4:2:0, one launch per direction.  A lane owns
 // one unit: an 8x8 pixel tile (4:4:4) or a 16x16 MCU (4:2:0), 64 units in
-// row-major unit order per wave.  nunits < 2^32.
+// row-major unit order per wave.  nunits < 2^32.  The unit grid covers the
+// padded frame (height and width rounded up to whole units); the kernels
+// without kRgbClip read nunits, units_x and pitch only.
 struct RgbGrid {
     uint32_t nunits;
     uint32_t units_x;  // units per row of units
-    uint64_t width;    // pixels per image row
+    uint64_t pitch;    // bytes from one image row to the next (>= 3 * width)
+    uint64_t height;   // the frame's own rows and pixels per row
+    uint64_t width;
 };
+// whole units, base and pitch 8-byte aligned: the kernels without kRgbClip
+inline bool rgb_whole_aligned(const void* rgb, const RgbGrid& g, bool s420) {
+    const uint64_t side = s420 ? 16u : 8u;
+    return g.height % side == 0u && g.width % side == 0u && g.pitch % 8u == 0u &&
+           reinterpret_cast<uintptr_t>(rgb) % 8u == 0u;
+}
 // Forward: built-in T, level shift 128; Y quantised with ql, Cb and Cr with qc
 // (qmode_* as launch_fdct; the caller proved |q| <= 32767 for both tables).
 hipError_t launch_fdct_rgb(const uint8_t* rgb, int16_t* y, int16_t* cb, int16_t* cr, const RgbGrid& g, bool s420,
@@ -216,6 +229,13 @@ hipError_t launch_fdct_rgb_420(const uint8_t* rgb, int16_t* y, int16_t* cb, int1
 hipError_t launch_fdct_rgb_444(const uint8_t* rgb, int16_t* y, int16_t* cb, int16_t* cr, const RgbGrid& g,
                                const QParams& ql, const QParams& qc, bool natural, const policy::Choice& c,
                                hipStream_t s);
+// the same with kRgbClip (hpdct_rgb_fwd420_clip.hip / hpdct_rgb_fwd444_clip.hip)
+hipError_t launch_fdct_rgb_420_clip(const uint8_t* rgb, int16_t* y, int16_t* cb, int16_t* cr, const RgbGrid& g,
+                                    const QParams& ql, const QParams& qc, bool natural, const policy::Choice& c,
+                                    hipStream_t s);
+hipError_t launch_fdct_rgb_444_clip(const uint8_t* rgb, int16_t* y, int16_t* cb, int16_t* cr, const RgbGrid& g,
+                                    const QParams& ql, const QParams& qc, bool natural, const policy::Choice& c,
+                                    hipStream_t s);
 
 hipError_t launch_fill_hash(uint8_t* out, uint64_t n, uint64_t seed, uint64_t first, hipStream_t s);
 

@@ -303,6 +303,10 @@ struct RgbCall {
     uint32_t units = 0;
     bool s420 = false;
     int qmode_luma = 0, qmode_chroma = 0;  // forward only; chroma 0 or 1
+    // units counts the padded unit grid.  clip: the frame is not whole units, or
+    // its base or row pitch is not 8-byte aligned (rgb_whole_aligned is false):
+    // the same launch shape with kRgbClip, the kernels' general instantiation
+    bool clip = false;
 };
 constexpr uint32_t rgb_waves(const RgbCall& c) { return c.units / 64u + (c.units % 64u != 0u); }
 // Forward: block stores LDS-staged into 1 KiB runs (kBlkStaged, as the plane
@@ -313,13 +317,14 @@ constexpr unsigned kRgbFwdVar = with_block<256>(kVarNT) | kBlkStaged;
 inline Choice forward_rgb(const RgbCall& c) {
     const bool fast = c.qmode_luma != 0 && c.qmode_chroma != 0;
     return uncapped(Family::kRgb,
-                    kRgbFwdVar | (c.s420 ? kRgb420 : 0u) | (fast ? quot_bits(c.qmode_luma) | kRgbChromaFastDiv : 0u),
+                    kRgbFwdVar | (c.s420 ? kRgb420 : 0u) | (fast ? quot_bits(c.qmode_luma) | kRgbChromaFastDiv : 0u) |
+                        (c.clip ? kRgbClip : 0u),
                     rgb_waves(c));
 }
 // Inverse: per-lane loads of whole blocks, plain per-lane RGB row stores
 constexpr unsigned kRgbInvVar = with_block<256>(0u);
 inline Choice inverse_rgb(const RgbCall& c) {
-    return uncapped(Family::kRgb, kRgbInvVar | (c.s420 ? kRgb420 : 0u), rgb_waves(c));
+    return uncapped(Family::kRgb, kRgbInvVar | (c.s420 ? kRgb420 : 0u) | (c.clip ? kRgbClip : 0u), rgb_waves(c));
 }
 
 // launch_roundtrip.  The two-lanes-per-tile round trip (hpdct_rt_duo.hpp) for

@@ -37,6 +37,16 @@
 // eight different 16-B columns, the sixteen lanes of a ds_read_b128 group read
 // two whole 128-B blocks.  Other sets (a ragged last one, 4:2:0 Y sets over two
 // MCU rows) store their blocks straight from the lane.
+//
+// Frames of any size and row pitch (hpdct_forward_rgb_frame / _inverse_rgb_frame).
+// The unit grid covers the frame padded to whole units, RgbGrid carries the row
+// pitch and the frame's own height and width.  Whole units with an 8-byte
+// aligned base and pitch run the kernels as above; anything else runs the
+// kRgbClip instantiation: a tile cut by the frame's edge (or every tile, when
+// base or pitch is not 8-byte aligned) is loaded byte by byte from clamped
+// coordinates (the last column and row repeated) and stored byte by byte below
+// 3 * width, rows beyond the height not at all.  Unit and block indices, and so
+// the staged block stores, are the same in both.
 #pragma once
 
 #include "hpdct_blocks.hpp"
@@ -54,6 +64,29 @@ struct RawRgb {
             r[i][0] = src[0];
             r[i][1] = src[1];
             r[i][2] = src[2];
+        });
+    }
+    // The same tile for any base and pitch, edge-replicated: the tile's first
+    // pixel is (y0, x0) of the padded frame, byte kB of row kI comes from row
+    // min(y0 + kI, h - 1), pixel min(x0 + kB / 3, w - 1) of the h x w frame.
+    // Byte loads (kRgbClip: edge units, and every unit of an unaligned frame).
+    __device__ __forceinline__ void load_clamped(const uint8_t* __restrict__ rgb, uint64_t pitch, uint64_t h,
+                                                 uint64_t w, uint64_t y0, uint64_t x0) {
+        const uint64_t xc = x0 < w ? x0 : w - 1u;
+        uint32_t xo[8];  // byte offset of pixel j from pixel xc
+        unroll<8>([&](auto j) { xo[j] = x0 + j < w ? 3u * j : 3u * static_cast<uint32_t>(w - 1u - xc); });
+        unroll<8>([&](auto i) {
+            const uint64_t y = y0 + i < h ? y0 + i : h - 1u;
+            const uint8_t* const row = rgb + y * pitch + 3u * xc;
+            uint32_t px[8];  // B << 16 | G << 8 | R
+            unroll<8>([&](auto j) {
+                const uint8_t* const p = row + xo[j];
+                px[j] = static_cast<uint32_t>(p[0]) | (static_cast<uint32_t>(p[1]) << 8) |
+                        (static_cast<uint32_t>(p[2]) << 16);
+            });
+            r[i][0] = make_uint2(px[0] | (px[1] << 24), (px[1] >> 8) | (px[2] << 16));
+            r[i][1] = make_uint2((px[2] >> 16) | (px[3] << 8), px[4] | (px[5] << 24));
+            r[i][2] = make_uint2((px[5] >> 8) | (px[6] << 16), (px[6] >> 16) | (px[7] << 8));
         });
     }
     // byte kB (0..23) of row kI
@@ -226,7 +259,11 @@ __device__ __forceinline__ void rgb_stage_flush(const char* image, char* run, ui
 
 // ---------------------------------------------------------------------------
 // Forward.  kVar: kRgb420, the luma quotient bits (kVarFastDiv, kVarJpegQ),
-// kRgbChromaFastDiv, kVarNT, kBlkStaged and the workgroup size.
+// kRgbChromaFastDiv, kVarNT, kBlkStaged, kRgbClip and the workgroup size.
+// kRgbClip: the unit grid covers the frame padded to whole units, and a tile
+// that the frame's edge cuts (or every tile, when base or pitch is not 8-byte
+// aligned) is loaded by RawRgb::load_clamped; a tile inside the frame keeps
+// the 8-byte loads.  Everything behind the load is the same code.
 // ---------------------------------------------------------------------------
 template <bool kNatural, unsigned kVar>
 __global__ __launch_bounds__(kBlock<kVar>, (kVar & kRgb420) != 0 ? 2 : 3) void fdct_rgb_kernel(const uint8_t* __restrict__ rgb,
@@ -236,6 +273,7 @@ __global__ __launch_bounds__(kBlock<kVar>, (kVar & kRgb420) != 0 ? 2 : 3) void f
     constexpr bool k420 = (kVar & kRgb420) != 0;
     constexpr bool kNT = (kVar & kVarNT) != 0;
     constexpr bool kStaged = (kVar & kBlkStaged) != 0;
+    constexpr bool kClip = (kVar & kRgbClip) != 0;
     constexpr unsigned kQL = kVar & (kVarFastDiv | kVarJpegQ);
     constexpr unsigned kQC = (kVar & kRgbChromaFastDiv) != 0 ? kVarFastDiv : 0u;
     constexpr uint32_t kSide = k420 ? 16u : 8u;  // pixels per unit side
@@ -248,8 +286,21 @@ __global__ __launch_bounds__(kBlock<kVar>, (kVar & kRgb420) != 0 ? 2 : 3) void f
     if (u0 + lane >= g.nunits) return;
     const uint32_t unit = u0 + lane;
     const uint32_t uy = unit / g.units_x, ux = unit - uy * g.units_x;
-    const uint64_t pitch = 3u * g.width;  // 64-bit byte offsets throughout: 3 H W passes 2^32
+    const uint64_t pitch = g.pitch;  // 64-bit byte offsets throughout: 3 H W passes 2^32
     const uint8_t* const src = rgb + static_cast<uint64_t>(uy) * kSide * pitch + static_cast<uint64_t>(ux) * kSide * 3u;
+    const bool aligned8 = !kClip || ((reinterpret_cast<uintptr_t>(rgb) | pitch) & 7u) == 0u;  // wave-uniform
+    // Y tile (tr, tc) of the unit
+    auto load_tile = [&](RawRgb& raw, uint32_t tr, uint32_t tc) {
+        const uint8_t* const p = src + static_cast<uint64_t>(tr) * 8u * pitch + tc * 24u;
+        if constexpr (kClip) {
+            const uint64_t y0 = static_cast<uint64_t>(uy) * kSide + 8u * tr, x0 = static_cast<uint64_t>(ux) * kSide + 8u * tc;
+            if (!aligned8 || y0 + 8u > g.height || x0 + 8u > g.width) {
+                raw.load_clamped(rgb, pitch, g.height, g.width, y0, x0);
+                return;
+            }
+        }
+        raw.load(p, pitch);
+    };
     // every lane of the wave is live (the staged stores need all 64)
     const bool whole = g.nunits - u0 >= 64u;
 
@@ -262,7 +313,7 @@ __global__ __launch_bounds__(kBlock<kVar>, (kVar & kRgb420) != 0 ? 2 : 3) void f
 
     if constexpr (!k420) {
         RawRgb raw;
-        raw.load(src, pitch);
+        load_tile(raw, 0u, 0u);
         float p[8][8];
         rgb_convert_tile<false>(raw, [&](auto i, const float (&xr)[8]) { fdct_feed_row<i>(T, xr, p); }, cb, cr);
         uint32_t w[32];
@@ -279,14 +330,12 @@ __global__ __launch_bounds__(kBlock<kVar>, (kVar & kRgb420) != 0 ? 2 : 3) void f
         const uint32_t uy0 = u0 / g.units_x, ux0 = u0 - uy0 * g.units_x;  // the set's first MCU
         const bool one_row = whole && g.units_x - ux0 >= 64u;
         RawRgb cur;
-        cur.load(src, pitch);
+        load_tile(cur, 0u, 0u);
 #pragma clang loop unroll(disable)
         for (int k = 0; k < kYTiles; ++k) {
             const uint32_t r = static_cast<uint32_t>(k) >> 1, c = static_cast<uint32_t>(k) & 1u;
             RawRgb nxt = cur;
-            if (k + 1 < kYTiles)
-                nxt.load(src + static_cast<uint64_t>((k + 1) >> 1) * 8u * pitch + static_cast<uint32_t>((k + 1) & 1) * 24u,
-                         pitch);
+            if (k + 1 < kYTiles) load_tile(nxt, static_cast<uint32_t>((k + 1) >> 1), static_cast<uint32_t>((k + 1) & 1));
             float p[8][8];
             uint32_t nb[4], nr[4];
             rgb_convert_tile<true>(cur, [&](auto i, const float (&xr)[8]) { fdct_feed_row<i>(T, xr, p); }, nb, nr);
@@ -339,7 +388,10 @@ __global__ __launch_bounds__(kBlock<kVar>, (kVar & kRgb420) != 0 ? 2 : 3) void f
 }
 
 // ---------------------------------------------------------------------------
-// Inverse.  kVar: kRgb420, kVarNT (the RGB stores) and the workgroup size.
+// Inverse.  kVar: kRgb420, kVarNT (the RGB stores), kRgbClip and the workgroup
+// size.  kRgbClip: rows at or beyond the frame's height are not stored, and a
+// row that the width cuts (or every row, when base or pitch is not 8-byte
+// aligned) is stored byte by byte, below 3 * width only.
 // The chroma tiles first, kept as packed uint8 (clamp + truncate: the values
 // hpdct_inverse_blocks gives for HPDCT_U8), then each Y tile's RGB rows: three
 // 8-B stores per row and lane.
@@ -367,6 +419,7 @@ __global__ __launch_bounds__(kBlock<kVar>, 1) void idct_rgb_kernel(const int16_t
                                                                 Mat64 qc) {
     constexpr bool k420 = (kVar & kRgb420) != 0;
     constexpr bool kNT = (kVar & kVarNT) != 0;
+    constexpr bool kClip = (kVar & kRgbClip) != 0;
     constexpr uint32_t kSide = k420 ? 16u : 8u;
     constexpr int kYTiles = k420 ? 4 : 1;
 
@@ -376,7 +429,8 @@ __global__ __launch_bounds__(kBlock<kVar>, 1) void idct_rgb_kernel(const int16_t
     if (wave * 64u + lane >= g.nunits) return;
     const uint32_t unit = wave * 64u + lane;
     const uint32_t uy = unit / g.units_x, ux = unit - uy * g.units_x;
-    const uint64_t pitch = 3u * g.width;
+    const uint64_t pitch = g.pitch;
+    const bool aligned8 = !kClip || ((reinterpret_cast<uintptr_t>(rgb) | pitch) & 7u) == 0u;  // wave-uniform
     uint8_t* const dst = rgb + static_cast<uint64_t>(uy) * kSide * pitch + static_cast<uint64_t>(ux) * kSide * 3u;
     const uint32_t tiles_x = (k420 ? 2u : 1u) * g.units_x;
 
@@ -399,6 +453,15 @@ __global__ __launch_bounds__(kBlock<kVar>, 1) void idct_rgb_kernel(const int16_t
 #pragma clang loop unroll(disable)
     for (int k = 0; k < kYTiles; ++k) {
         const uint32_t r = static_cast<uint32_t>(k) >> 1, c = static_cast<uint32_t>(k) & 1u;
+        // the tile's first pixel in the padded frame; kRgbClip: rows and bytes of the tile inside the frame
+        const uint64_t y0 = static_cast<uint64_t>(uy) * kSide + 8u * r, x0 = static_cast<uint64_t>(ux) * kSide + 8u * c;
+        uint32_t live_rows = 8u, live_bytes = 24u;
+        if constexpr (kClip) {
+            if (y0 >= g.height || x0 >= g.width) continue;  // a tile of padding only
+            live_rows = static_cast<uint32_t>(g.height - y0 < 8u ? g.height - y0 : 8u);
+            live_bytes = 3u * static_cast<uint32_t>(g.width - x0 < 8u ? g.width - x0 : 8u);
+        }
+        const bool whole_rows = aligned8 && live_bytes == 24u;
         const uint64_t t = static_cast<uint64_t>((k420 ? 2u : 1u) * uy + r) * tiles_x + (k420 ? 2u : 1u) * ux + c;
         const uint4* const src = reinterpret_cast<const uint4*>(reinterpret_cast<const char*>(yb) + t * 128u);
         // 4:2:0: the tile's quadrant of the chroma tiles, rows 4 r .. 4 r + 3, columns 4 c .. 4 c + 3
@@ -424,6 +487,16 @@ __global__ __launch_bounds__(kBlock<kVar>, 1) void idct_rgb_kernel(const int16_t
                 px[3 * u + 1] = static_cast<uint32_t>(clamp255(y + ((-22554 * b - 46802 * rr2 + 32768) >> 16)));
                 px[3 * u + 2] = static_cast<uint32_t>(clamp255(y + ((116130 * b + 32768) >> 16)));
             });
+            if constexpr (kClip) {
+                if (static_cast<uint32_t>(v) >= live_rows) return;
+                if (!whole_rows) {
+                    uint8_t* const pb = out + v * pitch;
+                    unroll<24>([&](auto b) {
+                        if (static_cast<uint32_t>(b) < live_bytes) pb[b] = static_cast<uint8_t>(px[b]);
+                    });
+                    return;
+                }
+            }
             uint32_t o[6];
             unroll<6>([&](auto d) {
                 o[d] = px[4 * d] | (px[4 * d + 1] << 8) | (px[4 * d + 2] << 16) | (px[4 * d + 3] << 24);

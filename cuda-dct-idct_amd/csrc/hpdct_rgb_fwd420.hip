@@ -1,6 +1,7 @@
 // hpdct_rgb_fwd420.hip -- the 4:2:0 colour forward kernels (hpdct_rgb.hpp) and
 // launch_fdct_rgb, which asks the policy and hands 4:4:4 to
-// hpdct_rgb_fwd444.hip (two units, so the two compile in parallel).
+// hpdct_rgb_fwd444.hip and the kRgbClip instantiations to the two *_clip.hip
+// units (so the four compile in parallel).
 #include "hpdct_rgb_launch.hpp"
 
 namespace hpdct {
@@ -16,8 +17,13 @@ hipError_t launch_fdct_rgb(const uint8_t* rgb, int16_t* y, int16_t* cb, int16_t*
                            hipStream_t s) {
     policy::RgbCall pc;
     pc.units = g.nunits, pc.s420 = s420, pc.qmode_luma = qmode_luma, pc.qmode_chroma = qmode_chroma;
+    pc.clip = !rgb_whole_aligned(rgb, g, s420);
     const policy::Choice c = policy::forward_rgb(pc);
     if (c.family != policy::Family::kRgb) return hipErrorInvalidDeviceFunction;
+    if ((c.var & kRgbClip) != 0u) {
+        if (s420) return launch_fdct_rgb_420_clip(rgb, y, cb, cr, g, ql, qc, natural, c, s);
+        return launch_fdct_rgb_444_clip(rgb, y, cb, cr, g, ql, qc, natural, c, s);
+    }
     if (s420) return launch_fdct_rgb_420(rgb, y, cb, cr, g, ql, qc, natural, c, s);
     return launch_fdct_rgb_444(rgb, y, cb, cr, g, ql, qc, natural, c, s);
 }

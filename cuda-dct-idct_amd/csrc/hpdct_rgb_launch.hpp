@@ -1,6 +1,7 @@
 // hpdct_rgb_launch.hpp -- instantiates the colour forward kernels of one
 // subsampling as policy::forward_rgb chose (hpdct_rgb_fwd420.hip,
-// hpdct_rgb_fwd444.hip).
+// hpdct_rgb_fwd444.hip; their kRgbClip instantiations in hpdct_rgb_fwd420_clip.hip
+// and hpdct_rgb_fwd444_clip.hip, four units that compile side by side).
 #pragma once
 
 #include "hpdct_rgb.hpp"
@@ -8,8 +9,9 @@
 
 namespace hpdct {
 
-// kSub: kRgb420 or 0.  The quotient pairs of policy::forward_rgb: luma JPEG
-// forms or 3-op with the 3-op chroma quotient, or IEEE division for both.
+// kSub: kRgb420 or 0, with or without kRgbClip.  The quotient pairs of
+// policy::forward_rgb: luma JPEG forms or 3-op with the 3-op chroma quotient,
+// or IEEE division for both.
 template <unsigned kSub>
 hipError_t launch_fdct_rgb_as(const uint8_t* rgb, int16_t* y, int16_t* cb, int16_t* cr, const RgbGrid& g,
                               const QParams& ql, const QParams& qc, bool natural, const policy::Choice& c,

@@ -57,6 +57,7 @@ C_SYMBOLS = [
     "hpdct_roundtrip_release_sums", "hpdct_floor_probe", "hpdct_copy_ceiling",
     "hpdct_forward_blocks", "hpdct_inverse_blocks", "hpdct_zigzag_order",
     "hpdct_default_chroma_quant_table", "hpdct_forward_rgb_blocks", "hpdct_inverse_rgb_blocks",
+    "hpdct_rgb_frame_geometry", "hpdct_forward_rgb_frame", "hpdct_inverse_rgb_frame",
 ]
 MAPPINGS = {"auto": 0, "tile": 1, "octet": 2, "duo": 3}
 BASELINES = {"reference_3pass": 0, "fastappr_3pass": 1}
@@ -126,6 +127,12 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     for f in (lib.hpdct_forward_rgb_blocks, lib.hpdct_inverse_rgb_blocks):
         f.argtypes = [vp, vp, vp, vp, i64, i64, ctypes.c_int, vp, vp, ctypes.c_uint, vp]
         f.restype = ctypes.c_int
+    lib.hpdct_rgb_frame_geometry.argtypes = [i64, i64, ctypes.c_int, vp, vp, vp, vp]
+    lib.hpdct_rgb_frame_geometry.restype = ctypes.c_int
+    lib.hpdct_forward_rgb_frame.argtypes = [vp, i64, vp, vp, vp, i64, i64, ctypes.c_int, vp, vp, ctypes.c_uint, vp]
+    lib.hpdct_forward_rgb_frame.restype = ctypes.c_int
+    lib.hpdct_inverse_rgb_frame.argtypes = [vp, vp, vp, vp, i64, i64, i64, ctypes.c_int, vp, vp, ctypes.c_uint, vp]
+    lib.hpdct_inverse_rgb_frame.restype = ctypes.c_int
     lib.hpdct_status_string.restype = ctypes.c_char_p
     lib.hpdct_status_string.argtypes = [ctypes.c_int]
     lib.hpdct_last_error_string.restype = ctypes.c_char_p
@@ -632,6 +639,148 @@ def bind_rgb_blocks(direction: str, rgb, y, cb, cr, *, subsampling: str = "420",
     else:
         fn, ptrs = lib.hpdct_inverse_rgb_blocks, (y.data_ptr(), cb.data_ptr(), cr.data_ptr(), rgb.data_ptr())
     return _rgb_call(fn, ptrs, h, w, sub, _host_table(q_luma), _host_table(q_chroma), flags, stream)
+
+
+# ---------------------------------------------------------------------------
+# Colour frames of any size and row pitch (hpdct_forward_rgb_frame /
+# hpdct_inverse_rgb_frame): edge-replicated to whole units, cropped on the way back
+# ---------------------------------------------------------------------------
+def rgb_frame_geometry(height: int, width: int, subsampling: str = "420"):
+    """(padded_height, padded_width, y_blocks, chroma_blocks) of a height x width
+    frame (hpdct_rgb_frame_geometry): the sizes rounded up to 8 ("444") or 16
+    ("420") and the block counts of the three arrays."""
+    out = [ctypes.c_int64() for _ in range(4)]
+    _check(load_library().hpdct_rgb_frame_geometry(int(height), int(width), _subsampling(subsampling),
+                                                   *[ctypes.byref(o) for o in out]))
+    return tuple(int(o.value) for o in out)
+
+
+def _rgb_frame_view(rgb, what: str, device):
+    """(h, w, pitch_bytes) of an (H, W, 3) uint8 device tensor whose pixels are
+    dense (stride(2) == 1, stride(1) == 3) and whose rows lie stride(0) >= 3 W
+    bytes apart: a whole frame, or a row- and column-sliced view of one."""
+    torch = _torch()
+    if not hasattr(rgb, "is_cuda") or not rgb.is_cuda:
+        raise HpdctError(1, f"{what} must be a CUDA tensor")
+    if device is not None and rgb.device != device:
+        raise HpdctError(1, f"{what} is on {rgb.device}, the source on {device}")
+    if rgb.dtype != torch.uint8:
+        raise HpdctError(2, f"{what} dtype {rgb.dtype} not in {[torch.uint8]}")
+    if rgb.dim() != 3 or rgb.shape[-1] != 3:
+        raise HpdctError(1, f"the {what} frame must be shaped (H, W, 3)")
+    h, w = int(rgb.shape[0]), int(rgb.shape[1])
+    if h <= 0 or w <= 0:
+        raise HpdctError(1, f"height and width must be positive (got {h}x{w})")
+    s0, s1, s2 = (int(s) for s in rgb.stride())
+    if s2 != 1 or (w > 1 and s1 != 3):
+        raise HpdctError(1, f"{what} must hold interleaved pixels: stride(2) == 1 and stride(1) == 3 "
+                            f"(got strides {(s0, s1, s2)})")
+    if h == 1:
+        s0 = 3 * w          # a single row: its stride is never used
+    if s0 < 3 * w:
+        raise HpdctError(1, f"{what} rows must lie at least 3*W = {3 * w} bytes apart (stride(0) is {s0})")
+    return h, w, s0
+
+
+def _rgb_frame_blocks(rgb, extent: int, y, cb, cr, geometry):
+    """Buffer checks of the three block arrays of a frame launch, those of
+    _rgb_planes against the padded geometry, and the overlap with the pitched
+    RGB extent."""
+    torch = _torch()
+    _, _, yb, cbk = geometry
+    for t, what, need in ((y, "y blocks", 64 * yb), (cb, "cb blocks", 64 * cbk), (cr, "cr blocks", 64 * cbk)):
+        _device_plane(t, what, rgb.device, need, (torch.int16,))
+    spans = [(t.data_ptr(), t.data_ptr() + n, what) for t, n, what in
+             ((rgb, extent, "rgb"), (y, 128 * yb, "y"), (cb, 128 * cbk, "cb"), (cr, 128 * cbk, "cr"))]
+    for i in range(4):
+        for j in range(i + 1, 4):
+            if spans[i][0] < spans[j][1] and spans[j][0] < spans[i][1]:
+                raise HpdctError(1, f"the {spans[i][2]} and {spans[j][2]} buffers overlap")
+
+
+def _rgb_frame_shapes(geometry, sub: int):
+    hp, wp, _, _ = geometry
+    ch, cw = (hp // 2, wp // 2) if sub == 1 else (hp, wp)
+    return (hp // 8, wp // 8, 64), (ch // 8, cw // 8, 64)
+
+
+def _rgb_frame_call(direction, rgb, pitch, y, cb, cr, h, w, sub, ql, qc, flags, stream):
+    lib = load_library()
+    vp = ctypes.c_void_p
+    tail = (h, w, sub, None if ql is None else ql.ctypes.data, None if qc is None else qc.ctypes.data, flags,
+            _stream_ptr(stream))
+    if direction == "fwd":
+        fn = lib.hpdct_forward_rgb_frame
+        args = (vp(rgb.data_ptr()), pitch, vp(y.data_ptr()), vp(cb.data_ptr()), vp(cr.data_ptr())) + tail
+    else:
+        fn = lib.hpdct_inverse_rgb_frame
+        args = (vp(y.data_ptr()), vp(cb.data_ptr()), vp(cr.data_ptr()), vp(rgb.data_ptr()), pitch) + tail
+
+    def call():
+        st = fn(*args)
+        if st:
+            _check(st)
+    call.tables = (ql, qc)  # the host tables live as long as the callable
+    return call
+
+
+def forward_rgb_frame(rgb, *, subsampling: str = "420", q_luma=None, q_chroma=None, order: str = "zigzag",
+                      out=None, stream=None):
+    """forward_rgb_blocks for an (H, W, 3) uint8 frame of any size, row pitch
+    and alignment (a row- or column-sliced view of a larger frame works without
+    a copy): the frame is extended to whole units by repeating its last column
+    and row, in the kernel.  Returns (y, cb, cr) shaped (Hp/8, Wp/8, 64) and
+    (Hc/8, Wc/8, 64), Hp x Wp from rgb_frame_geometry, Hc x Wc = Hp x Wp
+    ("444") or Hp/2 x Wp/2 ("420")."""
+    torch = _torch()
+    sub, flags = _subsampling(subsampling), _block_flags(order)
+    h, w, pitch = _rgb_frame_view(rgb, "rgb", None)
+    geometry = rgb_frame_geometry(h, w, subsampling)
+    if out is None:
+        ys, cs = _rgb_frame_shapes(geometry, sub)
+        out = (torch.empty(ys, dtype=torch.int16, device=rgb.device),
+               torch.empty(cs, dtype=torch.int16, device=rgb.device),
+               torch.empty(cs, dtype=torch.int16, device=rgb.device))
+    y, cb, cr = out
+    _rgb_frame_blocks(rgb, (h - 1) * pitch + 3 * w, y, cb, cr, geometry)
+    _rgb_frame_call("fwd", rgb, pitch, y, cb, cr, h, w, sub, _host_table(q_luma), _host_table(q_chroma), flags,
+                    stream)()
+    return y, cb, cr
+
+
+def inverse_rgb_frame(y, cb, cr, *, height: int, width: int, subsampling: str, q_luma=None, q_chroma=None,
+                      order: str = "zigzag", out=None, stream=None):
+    """inverse_rgb_blocks cropped to height x width: (y, cb, cr) hold the blocks
+    of the padded frame (rgb_frame_geometry), out is an (height, width, 3) uint8
+    tensor or view (any row pitch; bytes between the rows are left alone)."""
+    torch = _torch()
+    sub, flags = _subsampling(subsampling), _block_flags(order)
+    _device_plane(y, "y blocks", None, 0, (torch.int16,))
+    h, w = int(height), int(width)
+    geometry = rgb_frame_geometry(h, w, subsampling)
+    if out is None:
+        out = torch.empty((h, w, 3), dtype=torch.uint8, device=y.device)
+    oh, ow, pitch = _rgb_frame_view(out, "rgb", y.device)
+    if (oh, ow) != (h, w):
+        raise HpdctError(1, f"rgb is {oh}x{ow}, the frame {h}x{w}")
+    _rgb_frame_blocks(out, (h - 1) * pitch + 3 * w, y, cb, cr, geometry)
+    _rgb_frame_call("inv", out, pitch, y, cb, cr, h, w, sub, _host_table(q_luma), _host_table(q_chroma), flags,
+                    stream)()
+    return out
+
+
+def bind_rgb_frame(direction: str, rgb, y, cb, cr, *, subsampling: str = "420", q_luma=None, q_chroma=None,
+                   order: str = "zigzag", stream=None):
+    """Pre-resolved forward_rgb_frame ("fwd") or inverse_rgb_frame ("inv")
+    launch on the given buffers (rgb: the frame or view, read or written): a
+    zero-argument callable like bind_rgb_blocks(), for timing."""
+    if direction not in ("fwd", "inv"):
+        raise ValueError('direction must be "fwd" or "inv"')
+    sub, flags = _subsampling(subsampling), _block_flags(order)
+    h, w, pitch = _rgb_frame_view(rgb, "rgb", None)
+    _rgb_frame_blocks(rgb, (h - 1) * pitch + 3 * w, y, cb, cr, rgb_frame_geometry(h, w, subsampling))
+    return _rgb_frame_call(direction, rgb, pitch, y, cb, cr, h, w, sub, _host_table(q_luma), _host_table(q_chroma),
+                           flags, stream)
 
 
 SSE_F32_UNIT = 1.0 / 65536.0  # HPDCT_SSE_F32_UNIT

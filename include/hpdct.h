@@ -343,6 +343,55 @@ hpdct_status hpdct_inverse_rgb_blocks(const int16_t* d_y, const int16_t* d_cb, c
                                       int64_t height, int64_t width, hpdct_subsampling sub,
                                       const float* q_luma64, const float* q_chroma64, unsigned flags, void* stream);
 
+/* Colour frames of any size and row pitch: the two calls above for a frame
+ * that is not whole units, is a region of a larger frame, or has padded rows.
+ * As every JPEG codec defines it, the frame is extended to whole units (8x8
+ * tiles for 4:4:4, 16x16 MCUs for 4:2:0) by repeating its last column and its
+ * last row; the padded blocks are coded and the inverse crops.  Still one
+ * kernel launch per direction, no copy of the frame.
+ *   sizes   height, width >= 1, any value.  pitch_bytes >= 3*width, any value;
+ *           d_rgb has any alignment.  Row r starts at d_rgb + r*pitch_bytes;
+ *           byte 3*x + c of the row is channel c of pixel x.  The RGB extent,
+ *           for the overlap check, is (height-1)*pitch_bytes + 3*width bytes.
+ *   padded  Hp, Wp: height, width rounded up to a multiple of 8 (4:4:4) or 16
+ *           (4:2:0); (Hp/8)*(Wp/8) < 2^32.  The three block arrays are sized
+ *           and laid out for the Hp x Wp frame exactly as
+ *           hpdct_forward_rgb_blocks lays them out: Hp*Wp int16 for d_y, the
+ *           same (4:4:4) or a quarter (4:2:0) for d_cb and d_cr each; 16-byte
+ *           aligned.  hpdct_rgb_frame_geometry (host only) returns Hp, Wp and
+ *           the block counts Hp*Wp/64 and (4:2:0) Hp*Wp/256; each output
+ *           pointer may be NULL.
+ *   forward bit for bit what hpdct_forward_rgb_blocks writes for the Hp x Wp
+ *           frame P with P[r][x] = frame[min(r, height-1)][min(x, width-1)]:
+ *           replication first, then the conversion, then the 2x2 average (a
+ *           4:2:0 quad that straddles the edge averages replicated pixels).
+ *   inverse bit for bit the top-left height x width pixels of what
+ *           hpdct_inverse_rgb_blocks writes for the Hp x Wp block arrays.
+ *           Bytes 3*width .. pitch_bytes-1 of a row are not written, and
+ *           nothing past the last row's 3*width bytes is.
+ *   Tables, flags, subsampling, the quotient forms and the independence from
+ *   hpdct_set_mapping are those of the two calls above.  Refused with
+ *   HPDCT_ERROR_INVALID_VALUE: pitch_bytes < 3*width; a height or width below
+ *   1; the padded tile-count limit; a null pointer; a block pointer that is
+ *   not 16-byte aligned; buffers that overlap (the RGB buffer with its pitched
+ *   extent).  With Hp == height, Wp == width and pitch_bytes == 3*width the
+ *   call is hpdct_forward_rgb_blocks / hpdct_inverse_rgb_blocks without their
+ *   size and d_rgb alignment rules.
+ *   Speed: a frame of whole units whose d_rgb and pitch_bytes are multiples of
+ *   8 runs the same kernel as the calls above.  Other frames run a general
+ *   kernel: only the units cut by the frame's edge pay for it while d_rgb and
+ *   pitch_bytes are multiples of 8; with an unaligned base or pitch every unit
+ *   moves its RGB bytes one at a time: pad the pitch to a
+ *   multiple of 8 where the producer allows it. */
+hpdct_status hpdct_rgb_frame_geometry(int64_t height, int64_t width, hpdct_subsampling sub, int64_t* padded_height,
+                                      int64_t* padded_width, int64_t* y_blocks, int64_t* chroma_blocks);
+hpdct_status hpdct_forward_rgb_frame(const uint8_t* d_rgb, int64_t pitch_bytes, int16_t* d_y, int16_t* d_cb,
+                                     int16_t* d_cr, int64_t height, int64_t width, hpdct_subsampling sub,
+                                     const float* q_luma64, const float* q_chroma64, unsigned flags, void* stream);
+hpdct_status hpdct_inverse_rgb_frame(const int16_t* d_y, const int16_t* d_cb, const int16_t* d_cr, uint8_t* d_rgb,
+                                     int64_t pitch_bytes, int64_t height, int64_t width, hpdct_subsampling sub,
+                                     const float* q_luma64, const float* q_chroma64, unsigned flags, void* stream);
+
 /* Work mapping of the kernels (new; the reference has one fixed decomposition
  * per program).  Output is bit-identical in every mapping; only speed differs.
  *   AUTO   per frame: eight lanes per 8x8 tile ("octet") for frames below
