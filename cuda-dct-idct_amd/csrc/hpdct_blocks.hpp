@@ -12,7 +12,11 @@
 // forms of quantise_biased_at) with the final v_trunc_f32 replaced by the
 // truncating v_cvt_i32_f32, as the int8 wire format does: the same integers,
 // -0.0 becomes 0.  The inverse dequantises (float)q * Q and runs idct_tile with
-// the zero terms of T skipped (the operands are finite, as for int8).
+// the zero terms of T skipped.  That is exact only while q * Q and every
+// partial sum stay finite, which the table alone does not promise (any finite
+// entry is legal: 32767 * 2e34 is infinite, and 0 * inf is NaN in the
+// reference): the host launches the kVarFullChain variant, which keeps every
+// term, for a table that fails its criterion (skip_zero_exact, hpdct_api.cpp).
 #pragma once
 
 #include "hpdct_kernels_impl.hpp"
@@ -170,14 +174,15 @@ __global__ __launch_bounds__(kBlock<kVar>, 1) void fdct_blocks_kernel(const uint
 // ---------------------------------------------------------------------------
 // Inverse: int16 blocks -> pixels (TOut float: R + 128, no clamp; uint8_t:
 // clamp + truncate).  kVar: RowSink's bits (kVarNT, kVarLdsStore and
-// kVarStraddle for fp32 rows) and the workgroup size.  The lane loads its
+// kVarStraddle for fp32 rows), the workgroup size and kVarFullChain (every term
+// of T kept; clear: its zero entries skipped).  The lane loads its
 // block's 128 contiguous bytes; the halves sign-extend to fp32 straight into
 // their row-major places.
 // ---------------------------------------------------------------------------
 template <typename TOut, bool kNatural, unsigned kVar>
 __global__ __launch_bounds__(kBlock<kVar>, 1) void idct_blocks_kernel(const int16_t* __restrict__ blocks,
                                                                    TOut* __restrict__ out, TileGrid g, Mat64 q) {
-    const TSource<true, true> T(nullptr);
+    const TSource<true, (kVar & kVarFullChain) == 0> T(nullptr);
     float4* const slots = wave_slots<kVar>();
     const RowSink<kVar, TOut> sink{out, g.width, slots};
     const uint32_t lane = threadIdx.x & 63u;

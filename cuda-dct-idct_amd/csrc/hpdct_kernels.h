@@ -44,6 +44,11 @@ enum : unsigned {
                               // multiple of 512 px) stores two contiguous runs per instruction instead of
                               // 32 B per lane; launched only for such widths (the branch costs the
                               // power-of-two frames ~3 %, profiles/r01/ab_straddle.log)
+    kVarFullChain = 1u << 27, // integer-input inverses with the built-in T (int8 plane, int16 blocks, colour):
+                              // every term of T kept, zero entries too.  For a table so large that q * Q or
+                              // a partial sum may overflow (skip_zero_exact of hpdct_api.cpp fails): 0 * inf = NaN
+                              // as in the reference.  Clear: the zero terms are skipped.  (The tools use
+                              // this bit for a forward-only diagnostic of their own kernels.)
 };
 // the octet kernels' own variant bit (hpdct_octet.hpp)
 enum : unsigned {
@@ -116,9 +121,11 @@ hipError_t launch_fdct(const TIn* img, TOut* out, float* shifted, const TileGrid
 
 // dq_out (fp32 -> fp32 with dequantisation only, else nullptr): q*Q is also
 // written there (the in-place multiply of the cublasDCTv2 inverse).
+// full_chain: q fails the skip criterion for int8 coefficients (read for int8
+// input dequantised with the built-in T only: the kVarFullChain kernels).
 template <typename TIn, typename TOut, bool kDequant, bool kBuiltinT>
 hipError_t launch_idct(const TIn* coef, TOut* out, float* dq_out, const TileGrid& g, const float* t_dev,
-                       const Mat64& q, float shift, bool row_first, hipStream_t s);
+                       const Mat64& q, float shift, bool row_first, bool full_chain, hipStream_t s);
 
 // Round trip (hpdct_roundtrip.hpp): uint8 frame -> fp32 quantised
 // coefficients + optional reconstruction + optional quality sums, built-in T.
@@ -191,9 +198,10 @@ hipError_t launch_fdct_duo_u8_frames(const FrameTable<float>& ft, const TileGrid
 // as launch_fdct; the caller proved |q| <= 32767).
 hipError_t launch_fdct_blocks(const uint8_t* img, int16_t* blocks, const TileGrid& g, const QParams& qp, int qmode,
                               bool natural, hipStream_t s);
-// Inverse: blocks -> fp32 pixels (R + 128, no clamp; out_f32) or uint8 (clamp + truncate)
+// Inverse: blocks -> fp32 pixels (R + 128, no clamp; out_f32) or uint8 (clamp + truncate).
+// full_chain: q fails the skip criterion for int16 coefficients (the kVarFullChain kernel)
 hipError_t launch_idct_blocks(const int16_t* blocks, void* out, bool out_f32, const TileGrid& g, const Mat64& q,
-                              bool natural, hipStream_t s);
+                              bool natural, bool full_chain, hipStream_t s);
 
 // Colour frames (hpdct_rgb.hpp): interleaved uint8 RGB <-> three int16 block
 // arrays (Y, Cb, Cr), 4:4:4 or 4:2:0, one launch per direction.  A lane owns
@@ -219,9 +227,11 @@ inline bool rgb_whole_aligned(const void* rgb, const RgbGrid& g, bool s420) {
 hipError_t launch_fdct_rgb(const uint8_t* rgb, int16_t* y, int16_t* cb, int16_t* cr, const RgbGrid& g, bool s420,
                            const QParams& ql, const QParams& qc, int qmode_luma, int qmode_chroma, bool natural,
                            hipStream_t s);
-// Inverse: blocks -> uint8 components (clamp + truncate) -> RGB
+// Inverse: blocks -> uint8 components (clamp + truncate) -> RGB.  full_chain: ql or qc fails the skip
+// criterion for int16 coefficients (the kVarFullChain kernels)
 hipError_t launch_idct_rgb(const int16_t* y, const int16_t* cb, const int16_t* cr, uint8_t* rgb, const RgbGrid& g,
-                           bool s420, const Mat64& ql, const Mat64& qc, bool natural, hipStream_t s);
+                           bool s420, const Mat64& ql, const Mat64& qc, bool natural, bool full_chain,
+                           hipStream_t s);
 // the per-subsampling units of the forward (hpdct_rgb_fwd420.hip / hpdct_rgb_fwd444.hip), as c chose
 hipError_t launch_fdct_rgb_420(const uint8_t* rgb, int16_t* y, int16_t* cb, int16_t* cr, const RgbGrid& g,
                                const QParams& ql, const QParams& qc, bool natural, const policy::Choice& c,

@@ -43,7 +43,8 @@ __device__ __forceinline__ uint32_t pack_i8x4(float a, float b, float c, float d
 // two operations per pixel: v_cvt_u32_f32 truncates and saturates (NaN and
 // negatives -> 0, +inf -> 0xffffffff), then min(., 255) is written straight
 // into byte k of the packed word (SDWA dst_sel).  Same value for every fp32
-// input, NaN and infinities included (tests/test_gpu_parity.py extremes).
+// input, NaN and infinities included (tests/test_gpu_decoder_input.py:
+// non-finite fp32 coefficients and the huge-table cases, every mapping).
 __device__ __forceinline__ uint32_t cvt_u32_sat(float x) {
     uint32_t t;
     asm("v_cvt_u32_f32 %0, %1" : "=v"(t) : "v"(x));
@@ -650,7 +651,9 @@ template <typename TIn, typename TOut, bool kDequant, bool kBuiltinT, unsigned k
 __global__ __launch_bounds__(kBlock<kVar>, 1) void idct_kernel(const TIn* __restrict__ coef, TOut* __restrict__ out,
                                                             float* __restrict__ dq_out, TileGrid g,
                                                             const float* __restrict__ t_dev, Mat64 q, float shift) {
-    constexpr bool kSkipZero = std::is_same_v<TIn, int8_t>;
+    // int8 coefficients skip the zero terms of the built-in T unless the host found that q * Q or a partial
+    // sum may overflow under the table in force (kVarFullChain)
+    constexpr bool kSkipZero = std::is_same_v<TIn, int8_t> && (kVar & kVarFullChain) == 0;
     const TSource<kBuiltinT, kSkipZero> T(t_dev);
     float4* const slots = wave_slots<kVar>();
     const RowSink<kVar, TOut> sink{out, g.width, slots};

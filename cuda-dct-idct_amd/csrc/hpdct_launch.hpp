@@ -108,17 +108,31 @@ hipError_t launch_fdct_impl(const TIn* img, TOut* out, float* shifted, const Til
 
 template <typename TIn, typename TOut, bool kDequant, bool kBuiltinT>
 hipError_t launch_idct_impl(const TIn* coef, TOut* out, float* dq_out, const TileGrid& g, const float* t_dev,
-                            const Mat64& q, float shift, bool row_first, hipStream_t s) {
+                            const Mat64& q, float shift, bool row_first, bool full_chain, hipStream_t s) {
     using policy::Family;
     constexpr bool kF32 = std::is_same_v<TIn, float> && std::is_same_v<TOut, float>;
     constexpr bool kU8Out = std::is_same_v<TOut, uint8_t>;
     constexpr bool kDuoIn = std::is_same_v<TIn, float> && (kF32 || kU8Out);
     constexpr bool kStraddleOk = std::is_same_v<TIn, int8_t> && std::is_same_v<TOut, float> && kBuiltinT;
+    // the full-chain variants exist where zero terms are skipped at all: int8 in, dequantised, built-in T
+    constexpr bool kFullOk = std::is_same_v<TIn, int8_t> && kDequant && kBuiltinT;
     policy::Call pc;
     pc.g = g, pc.in = kElem<TIn>, pc.out = kElem<TOut>;
     pc.quant = kDequant, pc.builtin_t = kBuiltinT, pc.wb_dequant = dq_out != nullptr, pc.row_first = row_first;
-    pc.cus = device_cus(), pc.mapping = mapping_mode();
+    pc.cus = device_cus(), pc.mapping = mapping_mode(), pc.full_chain = full_chain;
     const policy::Choice c = policy::inverse(pc);
+    if constexpr (kFullOk) {
+        if ((c.var & kVarFullChain) != 0u) {
+            constexpr unsigned kV = policy::kInvFullVar;
+            if (c.family == Family::kOctet)
+                return launch_choice<kV, idct_octet_kernel<TIn, TOut, kDequant, kBuiltinT, kV>>(c, s, coef, out, dq_out,
+                                                                                                g, t_dev, q, shift);
+            if (c.family == Family::kTile)
+                return launch_choice<kV, idct_kernel<TIn, TOut, kDequant, kBuiltinT, kV>>(c, s, coef, out, dq_out, g,
+                                                                                          t_dev, q, shift);
+            return hipErrorInvalidDeviceFunction;
+        }
+    }
     switch (c.family) {
         case Family::kRowFirstDuo:
             if constexpr (kF32)

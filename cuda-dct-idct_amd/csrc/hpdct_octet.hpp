@@ -172,7 +172,7 @@ __global__ __launch_bounds__(kBlock<kVar>) void idct_octet_kernel(const TIn* __r
                                                                   float* __restrict__ dq_out, TileGrid g,
                                                                   const float* __restrict__ t_dev, Mat64 q,
                                                                   float shift) {
-    constexpr bool kSkipZero = std::is_same_v<TIn, int8_t>;
+    constexpr bool kSkipZero = std::is_same_v<TIn, int8_t> && (kVar & kVarFullChain) == 0;  // as idct_kernel
     const TSource<kBuiltinT, kSkipZero> T(t_dev);
     const float* qtab = kDequant ? stage_tables<kVar, 1>(q, nullptr) : nullptr;
     const uint32_t lane = threadIdx.x & 63u, t = lane >> 3, x = lane & 7u;

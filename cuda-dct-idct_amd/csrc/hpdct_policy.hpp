@@ -34,6 +34,9 @@ struct Call {
     bool quant = true, builtin_t = true, writeback = false, wb_dequant = false, row_first = false, shift128 = true;
     int qmode = 0, mapping = HPDCT_MAPPING_AUTO;
     uint32_t cus = 256;
+    // integer-input inverses with the built-in T: the table fails skip_zero_exact (hpdct_api.cpp) for the
+    // input type's range, so the kernel keeps every term of T (kVarFullChain)
+    bool full_chain = false;
 };
 // A round trip (launch_roundtrip).  slot: its sums have a spread slot.
 struct RtCall {
@@ -250,6 +253,11 @@ inline Choice forward_frames(const Call& c) {
     return uncapped(Family::kTile, var, sets, c.frames);
 }
 
+// The integer-input inverses (int8 plane, int16 blocks, colour) with the built-in T skip T's zero entries,
+// which is bit-exact while no operand or partial sum of the two passes can overflow.  A table that fails that
+// criterion (Call::full_chain, RgbCall::full_chain) takes this plain variant of the same kernel instead: every
+// term kept, 256-thread workgroups, per-lane stores, neither LDS staging nor non-temporal stores.
+constexpr unsigned kInvFullVar = with_block<256>(kVarFullChain);
 // launch_idct: fp32 or int8 coefficients in, fp32 or uint8 pixels out
 inline Choice inverse(const Call& c) {
     const bool f32 = c.in == Elem::kF32 && c.out == Elem::kF32;
@@ -262,6 +270,12 @@ inline Choice inverse(const Call& c) {
     // (8192^2 -> uint8: 61.8 -> 56.7 us, profiles/r01/mappings/kbench2_inv_i8.log)
     const bool duo_in = c.in == Elem::kF32 && (f32 || c.out == Elem::kU8);
     const Family map = pick_mapping(c, duo_in);
+    // int8 coefficients through a table that fails the skip criterion: the plain full-chain instantiation of
+    // the mapping's kernel (256-thread workgroups, per-lane stores; its speed does not matter)
+    if (c.full_chain && c.in == Elem::kI8 && c.quant && c.builtin_t) {
+        if (map == Family::kOctet) return uncapped(Family::kOctet, kInvFullVar, octet_waves(c.g));
+        return uncapped(Family::kTile, kInvFullVar, tile_waves(c.g));
+    }
     if (map == Family::kDuo) {
         // uint8 output: 512-thread workgroups (56.7 vs 57.6 us with 256), never capped
         const unsigned dv = (c.out == Elem::kU8 ? with_block<512>(kDuoVar) : kDuoVar) | wb;
@@ -291,6 +305,7 @@ constexpr unsigned blocks_inv_var(Elem out) {
     return with_block<256>(kVarNT) | (out == Elem::kF32 ? kVarLdsStore : 0u);
 }
 inline Choice inverse_blocks(const Call& c) {
+    if (c.full_chain) return uncapped(Family::kBlocks, kInvFullVar, tile_waves(c.g));
     const bool straddle = c.out == Elem::kF32 && c.g.tiles_x % 64u != 0u;
     return uncapped(Family::kBlocks, blocks_inv_var(c.out) | (straddle ? kVarStraddle : 0u), tile_waves(c.g));
 }
@@ -307,6 +322,8 @@ struct RgbCall {
     // its base or row pitch is not 8-byte aligned (rgb_whole_aligned is false):
     // the same launch shape with kRgbClip, the kernels' general instantiation
     bool clip = false;
+    // inverse only: a table fails the skip criterion for int16 blocks (kVarFullChain)
+    bool full_chain = false;
 };
 constexpr uint32_t rgb_waves(const RgbCall& c) { return c.units / 64u + (c.units % 64u != 0u); }
 // Forward: block stores LDS-staged into 1 KiB runs (kBlkStaged, as the plane
@@ -324,6 +341,8 @@ inline Choice forward_rgb(const RgbCall& c) {
 // Inverse: per-lane loads of whole blocks, plain per-lane RGB row stores
 constexpr unsigned kRgbInvVar = with_block<256>(0u);
 inline Choice inverse_rgb(const RgbCall& c) {
+    // the full chain: one instantiation per subsampling, the general one (kRgbClip takes whole aligned frames too)
+    if (c.full_chain) return uncapped(Family::kRgb, kInvFullVar | kRgbClip | (c.s420 ? kRgb420 : 0u), rgb_waves(c));
     return uncapped(Family::kRgb, kRgbInvVar | (c.s420 ? kRgb420 : 0u) | (c.clip ? kRgbClip : 0u), rgb_waves(c));
 }
 

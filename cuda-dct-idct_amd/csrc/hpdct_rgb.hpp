@@ -388,8 +388,8 @@ __global__ __launch_bounds__(kBlock<kVar>, (kVar & kRgb420) != 0 ? 2 : 3) void f
 }
 
 // ---------------------------------------------------------------------------
-// Inverse.  kVar: kRgb420, kVarNT (the RGB stores), kRgbClip and the workgroup
-// size.  kRgbClip: rows at or beyond the frame's height are not stored, and a
+// Inverse.  kVar: kRgb420, kVarNT (the RGB stores), kRgbClip, kVarFullChain
+// (as idct_blocks_kernel) and the workgroup size.  kRgbClip: rows at or beyond the frame's height are not stored, and a
 // row that the width cuts (or every row, when base or pitch is not 8-byte
 // aligned) is stored byte by byte, below 3 * width only.
 // The chroma tiles first, kept as packed uint8 (clamp + truncate: the values
@@ -434,7 +434,8 @@ __global__ __launch_bounds__(kBlock<kVar>, 1) void idct_rgb_kernel(const int16_t
     uint8_t* const dst = rgb + static_cast<uint64_t>(uy) * kSide * pitch + static_cast<uint64_t>(ux) * kSide * 3u;
     const uint32_t tiles_x = (k420 ? 2u : 1u) * g.units_x;
 
-    const TSource<true, true> T(nullptr);
+    // kVarFullChain: a table under which q * Q or a partial sum may overflow; every term of T kept
+    const TSource<true, (kVar & kVarFullChain) == 0> T(nullptr);
     // row v of a chroma tile: dwords 2 v (columns 0..3) and 2 v + 1
     uint32_t cb[16] = {}, cr[16] = {};
 #pragma clang loop unroll(disable)

@@ -5,11 +5,18 @@
 namespace hpdct {
 
 hipError_t launch_idct_rgb(const int16_t* y, const int16_t* cb, const int16_t* cr, uint8_t* rgb, const RgbGrid& g,
-                           bool s420, const Mat64& ql, const Mat64& qc, bool natural, hipStream_t s) {
+                           bool s420, const Mat64& ql, const Mat64& qc, bool natural, bool full_chain,
+                           hipStream_t s) {
     policy::RgbCall pc;
-    pc.units = g.nunits, pc.s420 = s420, pc.clip = !rgb_whole_aligned(rgb, g, s420);
+    pc.units = g.nunits, pc.s420 = s420, pc.clip = !rgb_whole_aligned(rgb, g, s420), pc.full_chain = full_chain;
     const policy::Choice c = policy::inverse_rgb(pc);
     if (c.family != policy::Family::kRgb) return hipErrorInvalidDeviceFunction;
+    if ((c.var & kVarFullChain) != 0u)  // the general instantiation only
+        return policy::with_bit<kRgb420, true>(c.var, [&](auto kS) {
+            constexpr unsigned kV = policy::kInvFullVar | kRgbClip | decltype(kS)::value;
+            if (natural) return launch_choice<kV, idct_rgb_kernel<true, kV>>(c, s, y, cb, cr, rgb, g, ql, qc);
+            return launch_choice<kV, idct_rgb_kernel<false, kV>>(c, s, y, cb, cr, rgb, g, ql, qc);
+        });
     return policy::with_bit<kRgb420, true>(c.var, [&](auto kS) {
         return policy::with_bit<kRgbClip, true>(c.var, [&](auto kC) {
             constexpr unsigned kV = policy::kRgbInvVar | decltype(kS)::value | decltype(kC)::value;

@@ -150,7 +150,11 @@ __global__ __launch_bounds__(kBlock, kRtWaves<kRecon>) void roundtrip_kernel(con
                               (kQMode == 2 ? kVarJpegQ : 0u) | (kStraddle ? kVarStraddle : 0u);
     // built-in T.  The forward's u8 pixels are finite, so the zero terms of T
     // are skipped exactly; so are the inverse's for kFast (int8-range q times
-    // Q in 1..255).  With IEEE division and a caller's table, q = round(C/Q)
+    // Q in 1..255: |q * Q| <= 127 * 255, far below any overflow, and a table
+    // large enough to fail the standalone inverses' skip criterion is no
+    // integer in 1..255, so it never reaches kFast: hpdct_api.cpp roundtrip
+    // asks for it only when fastdiv_ok and int8_ok hold).
+    // With IEEE division and a caller's table, q = round(C/Q)
     // may be +-inf (|Q| tiny): then the inverse runs the full chain, where
     // 0 * inf = NaN as in the reference and the standalone fp32 inverse.
     const TSource<true, true> T(nullptr);

@@ -155,7 +155,10 @@ __device__ __forceinline__ void rt_duo_body(const uint8_t* __restrict__ img, TC*
     // truncating convert does it), so D below is only right for fp32: the int8
     // kernel must be forward only (the compiler then drops the inverse)
     static_assert(!kI8 || (kRecon == kRtReconNone && !kStats), "int8 coefficients: forward only");
-    const TSource<true, true> T(nullptr);  // built-in T, zero terms skipped (finite operands)
+    // built-in T, zero terms skipped.  Exact here without a look at the table: this kernel runs with the
+    // verified quotient only (policy::roundtrip, qmode 1 or 2), i.e. an integer table in 1..255 and int8-range
+    // q, so the inverse's operands are |q * Q| <= 127 * 255 and no partial sum comes near overflow
+    const TSource<true, true> T(nullptr);
     const uint32_t lane = threadIdx.x & 63u;
     const uint8_t* const src = img + a.base;
 

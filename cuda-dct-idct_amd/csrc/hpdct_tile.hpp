@@ -15,11 +15,15 @@
 // The whole library is compiled with -ffp-contract=off: every fused
 // multiply-add is an explicit __builtin_fmaf, nothing else may fuse.
 //
-// Zero terms of the built-in T are skipped only where the operand is known
-// finite (uint8 pixels, int8 coefficients): a chain that starts at +0 never
-// holds -0 under round-to-nearest, so fma(0, x, s) == s for finite x and the
-// skip is bit-exact.  fp32 inputs keep every term (an Inf/NaN input must
-// poison the same outputs as in the reference).
+// Zero terms of the built-in T are skipped only where every operand and
+// partial sum is known finite: a chain that starts at +0 never holds -0 under
+// round-to-nearest, so fma(0, x, s) == s for finite x and s and the skip is
+// bit-exact.  uint8 pixels are such operands.  Integer coefficients (int8,
+// int16) are not by themselves: the operand is q * Q, and any finite non-zero
+// Q is legal, so the host checks the table (skip_zero_exact, hpdct_api.cpp:
+// max|Q| * qmax * c^2 < FLT_MAX) and launches the full-chain variant
+// (kVarFullChain) of the inverse when it fails.  fp32 inputs keep every term
+// (an Inf/NaN input must poison the same outputs as in the reference).
 #pragma once
 
 #include <hip/hip_runtime.h>

@@ -91,7 +91,17 @@ void hpdct_default_transform(float* t64);
 /* Library-owned quantisation table used by every subsequent forward/inverse
  * call (process-wide).  q64: HOST pointer to 64 floats, row-major [v][u];
  * NULL restores the default JPEG luminance table.  Entries must be finite and
- * non-zero. */
+ * non-zero; negative entries are legal.
+ * The inverses agree with the reference bit for bit under any such table,
+ * also one so large that q*Q or a partial sum overflows (the reference then
+ * gives Inf, and NaN where an Inf meets a zero entry of T).  The integer-input
+ * inverses (HPDCT_I8 coefficients, int16 blocks, the colour calls; built-in T)
+ * skip the zero entries of T only while that cannot happen:
+ *     max|Q| * qmax * c^2 < FLT_MAX,
+ * c = 2.378 the largest column abs-sum of T, qmax = 128 for HPDCT_I8 and 32768
+ * for int16 blocks (max|Q| below 4.7e35 and 1.8e33; a colour call tests both
+ * of its tables).  A table beyond that runs kernels that keep every term:
+ * the same result by the same rule, at a lower speed. */
 hpdct_status hpdct_set_quant_table(const float* q64);
 hpdct_status hpdct_get_quant_table(float* q64);
 

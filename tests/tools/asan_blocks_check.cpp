@@ -53,6 +53,15 @@ int main() {
     expect("set 1/64 table", hpdct_set_quant_table(q), 0);
     expect("fwd range", hpdct_forward_blocks(A, B, 8, 8, 0, nullptr), 3, "int16");
     expect("restore table", hpdct_set_quant_table(nullptr), 0);
+    // a huge finite table is legal (the inverses take their full-chain kernels under it): the skip criterion
+    // is computed when the table is set, and a call is still judged by its arguments first
+    for (float& v : q) v = 2e34f;
+    q[5] = -3.0e38f;
+    expect("set huge table", hpdct_set_quant_table(q), 0);
+    expect("inv null under the huge table", hpdct_inverse_blocks(nullptr, A, HPDCT_U8, 8, 8, 0, nullptr), 1);
+    expect("inv 8x20 under the huge table", hpdct_inverse_blocks(B, A, HPDCT_F32, 8, 20, 0, nullptr), 1,
+           "multiples of 8");
+    expect("restore table", hpdct_set_quant_table(nullptr), 0);
 
     // exactly 64 bytes on the heap: a write past them is an ASan report
     std::unique_ptr<uint8_t[]> z(new uint8_t[64]);

@@ -50,6 +50,25 @@ int main() {
     expect("inv 8192x8200 -> u8", inverse_blocks(call(8192, 8200, Elem::kU8, 0)), kVarNT, 4100);
     expect("inv 1024^2 -> u8 forced duo", inverse_blocks(call(1024, 1024, Elem::kU8, 0, HPDCT_MAPPING_DUO)), kVarNT,
            64);
+    // a table that fails the skip criterion: the plain full-chain kernel for either output, whatever the width
+    for (Elem out : {Elem::kF32, Elem::kU8}) {
+        Call full = call(8192, 8200, out, 0);
+        full.full_chain = true;
+        expect("inv 8192x8200 full chain", inverse_blocks(full), kVarFullChain, 4100);
+        full = call(24, 1016, out, 0, HPDCT_MAPPING_OCTET);
+        full.full_chain = true;
+        expect("inv 24x1016 full chain forced octet", inverse_blocks(full), kVarFullChain, 2);
+    }
+    // the flag means nothing to the forward
+    {
+        Call fwd = call(8192, 8192, Elem::kU8, 2);
+        fwd.full_chain = true;
+        expect("fwd 8192^2 default table, full_chain set", forward_blocks(fwd), kFwd | kJ, 4096);
+    }
+    static_assert(kInvFullVar == kVarFullChain && block_of(kInvFullVar) == 256u, "the plain full-chain variant");
+    static_assert((kVarFullChain & (blocks_inv_var(Elem::kF32) | blocks_inv_var(Elem::kU8) | kVarStraddle | kBlocksFwdVar |
+                                    kVarFastDiv | kVarJpegQ)) == 0u,
+                  "kVarFullChain aliases a bit of the existing block kernels");
     if (g_bad != 0) {
         std::printf("policy_blocks_check: %d rows differ\n", g_bad);
         return 1;

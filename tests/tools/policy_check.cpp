@@ -155,6 +155,37 @@ int main() {
            4096);
     expect("inv i8->f32 4096x4104", inverse(fwd(4096, 4104, I8, F32, 0)), Family::kTile,
            with_block<512>(kTileF32 | kVarStraddle), 512, 0, 513);
+    // int8 coefficients under a table that fails the skip criterion: the plain full-chain variant of the
+    // mapping's kernel (256-thread workgroups, no staging, no straddle form), for either output
+    for (Elem out : {F32, U8}) {
+        Call c = fwd(4096, 4104, I8, out, 0);
+        c.full_chain = true;
+        expect("inv i8 4096x4104 full chain", inverse(c), Family::kTile, kVarFullChain, 256, 0, 1026);
+        c.mapping = OCTET;
+        expect("inv i8 4096x4104 full chain, forced octet", inverse(c), Family::kOctet, kVarFullChain, 256, 0, 8208);
+        c.mapping = DUO;  // no duo kernel takes int8: as AUTO
+        expect("inv i8 4096x4104 full chain, forced duo", inverse(c), Family::kTile, kVarFullChain, 256, 0, 1026);
+        c = fwd(1024, 1024, I8, out, 0);
+        c.full_chain = true;
+        expect("inv i8 1024^2 full chain (AUTO: octet)", inverse(c), Family::kOctet, kVarFullChain, 256, 0, 512);
+        // nothing is skipped without dequantisation or with a caller's T: the flag is not read
+        c = fwd(4096, 4096, I8, out, 0);
+        c.full_chain = true, c.quant = false;
+        expect("inv i8 4096^2 no dequant, full_chain set", inverse(c), Family::kTile, prod_var(out), 512, 0, 512);
+        c.quant = true, c.builtin_t = false;
+        expect("inv i8 4096^2 caller's T, full_chain set", inverse(c), Family::kTile, prod_var(out), 512, 0, 512);
+    }
+    {
+        // fp32 coefficients keep every term anyway: the flag is not read
+        Call c = fwd(8192, 8192, F32, F32, 0);
+        c.full_chain = true;
+        expect("inv f32->f32 8192^2, full_chain set", inverse(c), Family::kDuo, with_block<64>(kVarNT), 64, 10, 32768);
+    }
+    static_assert(kInvFullVar == kVarFullChain, "the plain full-chain variant: 256 threads, no other bit");
+    static_assert((kVarFullChain & (prod_var(F32) | prod_var(U8) | prod_var(I8) | oct_var(F32) | oct_var(U8) | kDuoVar |
+                                    kVarStraddle | kVarWbDequant | kVarRowFirst | kProductOnlyVarBits | kVarFastDiv |
+                                    kF32OneWaveForm | (3u << 12))) == 0u,
+                  "kVarFullChain aliases a bit of the existing plane kernels");
 
     // --- frame lists, uint8 -> fp32, qmode 2 ---
     {

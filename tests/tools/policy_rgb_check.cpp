@@ -60,6 +60,24 @@ int main() {
     expect("inv 444 8192^2", inverse_rgb(call(8192, 8192, false)), 0u, 4096);
     expect("inv 420 16x1040", inverse_rgb(call(16, 1040, true)), kRgb420, 1);
     expect("inv 444 24x1016 (381 tiles)", inverse_rgb(call(24, 1016, false)), 0u, 2);
+    // a table that fails the skip criterion: the full chain on the general (kRgbClip) instantiation
+    for (int s = 0; s < 2; ++s) {
+        RgbCall full = call(8192, 8192, s != 0);
+        full.full_chain = true;
+        expect("inv 8192^2 full chain", inverse_rgb(full), kVarFullChain | kRgbClip | (s != 0 ? kRgb420 : 0u),
+               s != 0 ? 1024 : 4096);
+        full.clip = true;
+        expect("inv 8192^2 full chain, clipped frame", inverse_rgb(full),
+               kVarFullChain | kRgbClip | (s != 0 ? kRgb420 : 0u), s != 0 ? 1024 : 4096);
+        // the flag means nothing to the forward
+        RgbCall fwd = call(8192, 8192, s != 0, 2, 1);
+        fwd.full_chain = true;
+        expect("fwd 8192^2 default tables, full_chain set", forward_rgb(fwd),
+               kFwd | (s != 0 ? kRgb420 : 0u) | kJ | kRgbChromaFastDiv, s != 0 ? 1024 : 4096);
+    }
+    static_assert((kVarFullChain & (kRgbFwdVar | kRgbInvVar | kRgb420 | kRgbChromaFastDiv | kRgbClip | kVarFastDiv |
+                                    kVarJpegQ)) == 0u,
+                  "kVarFullChain aliases a bit of the existing colour kernels");
     if (g_bad != 0) {
         std::printf("policy_rgb_check: %d rows differ\n", g_bad);
         return 1;

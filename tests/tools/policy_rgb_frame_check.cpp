@@ -109,6 +109,19 @@ int main() {
                 forward_rgb(dense(128, 1024, true, 2, 1)));
     expect_clip("inv 444 64x512 base + 4", inverse_rgb(call({64, 512, 3 * 512, kBase + 4, false})),
                 inverse_rgb(dense(64, 512, false)));
+    // a table that fails the skip criterion: one full-chain choice per padded grid, the general instantiation,
+    // for whole aligned frames and ragged ones alike
+    for (int s = 0; s < 2; ++s) {
+        const bool s420 = s != 0;
+        RgbCall whole = call({128, 1024, 3 * 1024, kBase, s420}), ragged = call({25, 1033, 3 * 1033, kBase, s420});
+        whole.full_chain = ragged.full_chain = true;
+        Choice want = inverse_rgb(dense(128, 1024, s420));
+        want.var |= kVarFullChain;
+        expect_clip("inv 128x1024 full chain", inverse_rgb(whole), want);
+        want = inverse_rgb(dense(32, 1040, s420));
+        want.var |= kVarFullChain;
+        expect_clip("inv 25x1033 full chain", inverse_rgb(ragged), want);
+    }
     // the numbers themselves, once: 1080p 4:2:0 is 68 x 120 = 8160 MCUs, 128 waves, 32 workgroups
     const Choice c = forward_rgb(call({1080, 1920, 3 * 1920, kBase, true}, 2, 1));
     if (c.grid_x != 32u || c.block != 256u || c.cap_wgs != 0u ||

@@ -190,7 +190,7 @@ void rt_two_kernels(const void* in, void* out, const Ctx& c, hipStream_t s) {
                        dim3(kBlock<kProdVar<uint8_t, float>>), 0, s, static_cast<const uint8_t*>(in), cf, nullptr, c.g,
                        nullptr, c.qp, 128.0f);
     (void)launch_idct_impl<float, uint8_t, true, true>(cf, static_cast<uint8_t*>(out), nullptr, c.g, nullptr, c.qp.q, 128.0f,
-                                            false, s);
+                                            false, false, s);
 }
 template <int kRecon, bool kStats, bool kFast>
 void rt_fused(const void* in, void* out, const Ctx& c, hipStream_t s) {
@@ -397,7 +397,7 @@ int main(int argc, char** argv) {
         CK(hipMemcpy(r8.data(), out[2], px, hipMemcpyDeviceToHost));
         CK(hipMemcpy(x.data(), img[1], px, hipMemcpyDeviceToHost));
         (void)launch_idct_impl<float, float, true, true>(g_coef2[1], static_cast<float*>(out[3]), nullptr, c.g, nullptr,
-                                              c.qp.q, 128.0f, false, 0);
+                                              c.qp.q, 128.0f, false, false, 0);
         CK(hipDeviceSynchronize());
         CK(hipMemcpy(rf.data(), out[3], px * 4, hipMemcpyDeviceToHost));
         CK(hipMemset(g_coef2[1], 0xff, px * 4));
