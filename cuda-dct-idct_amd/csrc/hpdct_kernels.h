@@ -72,6 +72,12 @@ enum : unsigned {
                                    // on the way in, cropped on the way out) or whose base or row pitch is not
                                    // 8-byte aligned; clear: whole units, 8-byte loads and stores everywhere
 };
+// the entropy coder's own variant bits (hpdct_scan.hpp)
+enum : unsigned {
+    kScanNatural = 1u << 25,  // the blocks are row-major inside (HPDCT_BLOCKS_NATURAL): permuted on load
+    kScanEmit = 1u << 28,     // scan_code_kernel: the emit launch (clear: the measure launch)
+    kScanOffsets = 1u << 29,  // scan_offsets_kernel
+};
 // Bits only the product kernels give a meaning to: the tools' A/B variant
 // bits must stay clear of them (static_assert in tools/kbench_variants.hpp).
 constexpr unsigned kProductOnlyVarBits = kVarFastDivChecked | kVarJpegQ;

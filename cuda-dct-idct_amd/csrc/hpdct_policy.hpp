@@ -15,7 +15,8 @@ namespace policy {
 // kDuoFwdU8: fdct_duo_u8(_frames)_kernel; kRt*: the round-trip kernels
 // kBlocks: fdct_blocks_kernel / idct_blocks_kernel (hpdct_blocks.hpp)
 // kRgb: fdct_rgb_kernel / idct_rgb_kernel (hpdct_rgb.hpp)
-enum class Family { kTile, kOctet, kDuo, kDuoFwdU8, kRowFirstDuo, kRtDuo, kRtTile, kBlocks, kRgb };
+// kScan: scan_code_kernel / scan_offsets_kernel (hpdct_scan.hpp)
+enum class Family { kTile, kOctet, kDuo, kDuoFwdU8, kRowFirstDuo, kRtDuo, kRtTile, kBlocks, kRgb, kScan };
 enum class Elem { kU8, kI8, kF32 };
 
 // var: the kernel's kVar; kDuoFwdU8 and kRt* carry their quotient and straddle bits there
@@ -345,6 +346,22 @@ inline Choice inverse_rgb(const RgbCall& c) {
     if (c.full_chain) return uncapped(Family::kRgb, kInvFullVar | kRgbClip | (c.s420 ? kRgb420 : 0u), rgb_waves(c));
     return uncapped(Family::kRgb, kRgbInvVar | (c.s420 ? kRgb420 : 0u) | (c.clip ? kRgbClip : 0u), rgb_waves(c));
 }
+
+// The entropy coder (hpdct_scan.hpp): its measure and emit launches run one
+// wave per restart interval in one-wave workgroups, no residency cap (a wave
+// holds 24 KiB of LDS: its bit buffer and its staged blocks); beyond
+// kScanMaxWgs intervals a workgroup takes every kScanMaxWgs-th one.  The
+// offsets launch is one 1024-thread workgroup.  hpdct_set_mapping is not read.
+struct ScanCall {
+    uint32_t intervals = 1;
+    bool natural = false;
+};
+constexpr uint32_t kScanMaxWgs = 1u << 20;
+inline Choice scan_code(const ScanCall& c, bool emit) {
+    return {Family::kScan, with_block<64>((c.natural ? kScanNatural : 0u) | (emit ? kScanEmit : 0u)), 64u, 0u,
+            c.intervals < kScanMaxWgs ? c.intervals : kScanMaxWgs, 1u};
+}
+inline Choice scan_offsets() { return {Family::kScan, with_block<1024>(kScanOffsets), 1024u, 0u, 1u, 1u}; }
 
 // launch_roundtrip.  The two-lanes-per-tile round trip (hpdct_rt_duo.hpp) for
 // the verified quotient (qmode 1 or 2) with any reconstruction, when its sums

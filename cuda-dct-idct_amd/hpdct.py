@@ -58,6 +58,8 @@ C_SYMBOLS = [
     "hpdct_forward_blocks", "hpdct_inverse_blocks", "hpdct_zigzag_order",
     "hpdct_default_chroma_quant_table", "hpdct_forward_rgb_blocks", "hpdct_inverse_rgb_blocks",
     "hpdct_rgb_frame_geometry", "hpdct_forward_rgb_frame", "hpdct_inverse_rgb_frame",
+    "hpdct_encode_scan", "hpdct_scan_bound", "hpdct_scan_workspace_bytes", "hpdct_jpeg_header",
+    "hpdct_huffman_table",
 ]
 MAPPINGS = {"auto": 0, "tile": 1, "octet": 2, "duo": 3}
 BASELINES = {"reference_3pass": 0, "fastappr_3pass": 1}
@@ -133,6 +135,17 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.hpdct_forward_rgb_frame.restype = ctypes.c_int
     lib.hpdct_inverse_rgb_frame.argtypes = [vp, vp, vp, vp, i64, i64, i64, ctypes.c_int, vp, vp, ctypes.c_uint, vp]
     lib.hpdct_inverse_rgb_frame.restype = ctypes.c_int
+    lib.hpdct_encode_scan.argtypes = [vp, vp, vp, i64, i64, ctypes.c_int, i64, ctypes.c_uint, vp, i64, vp, vp, vp, i64,
+                                      vp]
+    lib.hpdct_encode_scan.restype = ctypes.c_int
+    lib.hpdct_scan_bound.argtypes = [i64, i64]
+    lib.hpdct_scan_bound.restype = i64
+    lib.hpdct_scan_workspace_bytes.argtypes = [i64, i64, ctypes.c_int, ctypes.c_int, i64]
+    lib.hpdct_scan_workspace_bytes.restype = i64
+    lib.hpdct_jpeg_header.argtypes = [vp, i64, vp, i64, i64, ctypes.c_int, ctypes.c_int, vp, vp, i64]
+    lib.hpdct_jpeg_header.restype = ctypes.c_int
+    lib.hpdct_huffman_table.argtypes = [ctypes.c_int, vp, vp, vp]
+    lib.hpdct_huffman_table.restype = None
     lib.hpdct_status_string.restype = ctypes.c_char_p
     lib.hpdct_status_string.argtypes = [ctypes.c_int]
     lib.hpdct_last_error_string.restype = ctypes.c_char_p
@@ -781,6 +794,178 @@ def bind_rgb_frame(direction: str, rgb, y, cb, cr, *, subsampling: str = "420", 
     _rgb_frame_blocks(rgb, (h - 1) * pitch + 3 * w, y, cb, cr, rgb_frame_geometry(h, w, subsampling))
     return _rgb_frame_call(direction, rgb, pitch, y, cb, cr, h, w, sub, _host_table(q_luma), _host_table(q_chroma),
                            flags, stream)
+
+
+# ---------------------------------------------------------------------------
+# Baseline-JPEG entropy coding (hpdct_encode_scan) and the file around the scan
+# ---------------------------------------------------------------------------
+HUFFMAN_TABLES = {"dc_luma": 0, "ac_luma": 1, "dc_chroma": 2, "ac_chroma": 3}
+
+
+def scan_bound(blocks: int, intervals: int) -> int:
+    """Worst-case bytes of a scan of `blocks` blocks in `intervals` restart
+    intervals (hpdct_scan_bound): 415 * blocks + 4 * intervals."""
+    n = int(load_library().hpdct_scan_bound(int(blocks), int(intervals)))
+    if n < 0:
+        raise HpdctError(1, f"no scan bound for {blocks} blocks in {intervals} intervals")
+    return n
+
+
+def huffman_table(kind):
+    """(bits, vals) of an Annex K.3 table (hpdct_huffman_table): kind 0..3 or
+    "dc_luma", "ac_luma", "dc_chroma", "ac_chroma"; bits[l-1] codes of length
+    l, vals the symbols in code order."""
+    k = HUFFMAN_TABLES.get(kind, kind)
+    if k not in (0, 1, 2, 3):
+        raise ValueError(f"kind must be 0..3 or one of {sorted(HUFFMAN_TABLES)}")
+    bits, vals, n = np.zeros(16, np.uint8), np.zeros(256, np.uint8), ctypes.c_int(0)
+    load_library().hpdct_huffman_table(k, bits.ctypes.data, vals.ctypes.data, ctypes.addressof(n))
+    return bits, vals[:n.value].copy()
+
+
+def jpeg_header(height: int, width: int, *, components: int = 3, subsampling: str = "420", q_luma=None,
+                q_chroma=None, restart_interval: int = 0) -> bytes:
+    """SOI .. SOS of a baseline file for a scan of encode_scan (hpdct_jpeg_header):
+    height and width are the TRUE frame size; append the scan and FF D9."""
+    ql, qc = _host_table(q_luma), _host_table(q_chroma)
+    buf, n = np.zeros(1024, np.uint8), ctypes.c_int64(0)
+    _check(load_library().hpdct_jpeg_header(buf.ctypes.data, buf.size, ctypes.addressof(n), int(height), int(width),
+                                            int(components), _subsampling(subsampling),
+                                            None if ql is None else ql.ctypes.data,
+                                            None if qc is None else qc.ctypes.data, int(restart_interval)))
+    return buf[:n.value].tobytes()
+
+
+def _scan_planes(y, cb, cr, height, width, sub: int, restart_interval: int):
+    """Buffer checks of the block arrays of one scan (the C-ABI sees raw pointers
+    only); returns (h, w, components, blocks, intervals, workspace_bytes)."""
+    torch = _torch()
+    _device_plane(y, "y blocks", None, 0, (torch.int16,))
+    if (cb is None) != (cr is None):
+        raise HpdctError(1, "cb and cr are both given or both None")
+    if height is None or width is None:
+        if y.dim() != 3 or y.shape[-1] != 64:
+            raise HpdctError(1, "pass height and width for y blocks that are not (H/8, W/8, 64)")
+        height, width = 8 * y.shape[0], 8 * y.shape[1]
+    h, w = int(height), int(width)
+    components = 1 if cb is None else 3
+    side = 16 if components == 3 and sub == 1 else 8
+    if h <= 0 or w <= 0 or h % side or w % side:
+        raise HpdctError(1, f"height and width must be positive multiples of {side} (got {h}x{w})")
+    ri = int(restart_interval)
+    if not 0 <= ri <= 65535:
+        raise HpdctError(1, f"restart_interval must be 0..65535 (got {ri})")
+    _device_plane(y, "y blocks", None, h * w, (torch.int16,))
+    nmcu = (h // side) * (w // side)
+    blocks = h * w // 64
+    if components == 3:
+        for t, what in ((cb, "cb blocks"), (cr, "cr blocks")):
+            _device_plane(t, what, y.device, 64 * nmcu, (torch.int16,))
+        blocks += 2 * nmcu
+    intervals = 1 if ri == 0 else -(-nmcu // ri)
+    ws = int(load_library().hpdct_scan_workspace_bytes(h, w, components, sub, ri))
+    if ws < 0:
+        _check(1)
+    return h, w, components, blocks, intervals, ws
+
+
+def bind_scan(y, cb, cr, scan, info, offsets, workspace, *, height=None, width=None, subsampling: str = "420",
+              restart_interval: int = 0, order: str = "zigzag", capacity=None, stream=None):
+    """Pre-resolved hpdct_encode_scan launch on the given buffers: a
+    zero-argument callable like the other bind_* functions (three kernel
+    launches, no allocation: it can be captured into a graph).  scan: uint8,
+    `capacity` bytes of it (default: all) may be written; info: 16 bytes (two
+    int64); offsets: None or intervals + 1 int64; workspace: uint8."""
+    torch = _torch()
+    sub, flags = _subsampling(subsampling), _block_flags(order)
+    h, w, components, _, intervals, ws = _scan_planes(y, cb, cr, height, width, sub, restart_interval)
+    _device_plane(scan, "scan", y.device, 0, (torch.uint8,))
+    cap = scan.numel() if capacity is None else int(capacity)
+    if cap < 0 or cap > scan.numel():
+        raise HpdctError(1, f"capacity {cap} is not within the scan buffer's {scan.numel()} bytes")
+    _device_plane(info, "info", y.device, 2, (torch.int64,))
+    if offsets is not None:
+        _device_plane(offsets, "offsets", y.device, intervals + 1, (torch.int64,))
+    _device_plane(workspace, "workspace", y.device, ws, (torch.uint8,))
+    vp = ctypes.c_void_p
+    args = (vp(y.data_ptr()), None if cb is None else vp(cb.data_ptr()), None if cr is None else vp(cr.data_ptr()),
+            h, w, sub, int(restart_interval), flags, vp(scan.data_ptr()), cap, vp(info.data_ptr()),
+            None if offsets is None else vp(offsets.data_ptr()), vp(workspace.data_ptr()), workspace.numel(),
+            _stream_ptr(stream))
+    fn = load_library().hpdct_encode_scan
+
+    def call():
+        st = fn(*args)
+        if st:
+            _check(st)
+    return call
+
+
+def scan_info(info) -> dict:
+    """The hpdct_scan_info a bind_scan launch wrote (synchronises)."""
+    raw = info.cpu().numpy().view(np.uint32)
+    return {"bytes": int(raw[0]) | int(raw[1]) << 32, "truncated": int(raw[2]), "out_of_range": int(raw[3])}
+
+
+def encode_scan(y, cb=None, cr=None, *, height=None, width=None, subsampling: str = "420",
+                restart_interval: int = 0, order: str = "zigzag", out=None, stream=None):
+    """int16 blocks -> the bytes of one baseline Huffman scan, on the device.
+    y alone: grey; y, cb, cr: the arrays of forward_rgb_blocks / forward_rgb_frame
+    (height and width: the padded frame).  Returns (scan, info, offsets): the
+    uint8 device tensor trimmed to its length, {"bytes", "truncated",
+    "out_of_range"} and the int64 device tensor of intervals + 1 byte offsets.
+    Synchronises to read the length.  out: a uint8 buffer to fill; if the scan
+    does not fit it, info["truncated"] is 1, info["bytes"] the size needed and
+    the returned scan is empty.  Without out, a buffer of the blocks' own size
+    is tried first and the exact size after that."""
+    torch = _torch()
+    sub = _subsampling(subsampling)
+    _, _, _, blocks, intervals, ws = _scan_planes(y, cb, cr, height, width, sub, restart_interval)
+    info = torch.empty(2, dtype=torch.int64, device=y.device)
+    offsets = torch.empty(intervals + 1, dtype=torch.int64, device=y.device)
+    workspace = torch.empty(ws, dtype=torch.uint8, device=y.device)
+    buf = out if out is not None else torch.empty(min(scan_bound(blocks, intervals), 128 * blocks + 4 * intervals),
+                                                  dtype=torch.uint8, device=y.device)
+    while True:
+        bind_scan(y, cb, cr, buf, info, offsets, workspace, height=height, width=width, subsampling=subsampling,
+                  restart_interval=restart_interval, order=order, stream=stream)()
+        if stream is not None:
+            stream.synchronize()
+        res = scan_info(info)
+        if not res["truncated"]:
+            return buf[:res["bytes"]], res, offsets
+        if out is not None:
+            return buf[:0], res, offsets
+        buf = torch.empty(res["bytes"], dtype=torch.uint8, device=y.device)
+
+
+def jpeg_encode(image, *, subsampling: str = "420", q_luma=None, q_chroma=None, restart_interval=None) -> bytes:
+    """A whole baseline JPEG file from a device frame.  A 2-D uint8 tensor (sizes
+    multiples of 8) is a grey frame: forward_blocks under the library table
+    (set_quant_table), then encode_scan.  An (H, W, 3) tensor of any size goes
+    through forward_rgb_frame with the given tables and subsampling.
+    restart_interval None: one MCU row per interval, what the coder is tuned
+    for.  A standard decoder inverts with the exact DCT, so the file decodes to
+    an approximation of this library's own inverse."""
+    if image.dim() == 2:
+        if q_luma is not None or q_chroma is not None:
+            raise HpdctError(2, "a grey frame is coded with the library table (set_quant_table)")
+        h, w = int(image.shape[0]), int(image.shape[1])
+        blocks = (forward_blocks(image),)
+        hp, wp, components, mcu = h, w, 1, 8
+    else:
+        h, w, _ = _rgb_frame_view(image, "image", None)
+        blocks = forward_rgb_frame(image, subsampling=subsampling, q_luma=q_luma, q_chroma=q_chroma)
+        hp, wp, _, _ = rgb_frame_geometry(h, w, subsampling)
+        components, mcu = 3, 16 if subsampling == "420" else 8
+    ri = wp // mcu if restart_interval is None else int(restart_interval)
+    head = jpeg_header(h, w, components=components, subsampling=subsampling, q_luma=q_luma, q_chroma=q_chroma,
+                       restart_interval=ri)
+    scan, info, _ = encode_scan(*blocks, height=hp, width=wp, subsampling=subsampling, restart_interval=ri)
+    if info["out_of_range"]:
+        raise HpdctError(3, f"{info['out_of_range']} coefficients are beyond baseline JPEG's range "
+                            "(DC difference +-2047, AC +-1023): use a coarser quant table")
+    return head + scan.cpu().numpy().tobytes() + b"\xff\xd9"
 
 
 SSE_F32_UNIT = 1.0 / 65536.0  # HPDCT_SSE_F32_UNIT

@@ -402,6 +402,99 @@ hpdct_status hpdct_inverse_rgb_frame(const int16_t* d_y, const int16_t* d_cb, co
                                      int64_t pitch_bytes, int64_t height, int64_t width, hpdct_subsampling sub,
                                      const float* q_luma64, const float* q_chroma64, unsigned flags, void* stream);
 
+/* Baseline-JPEG entropy coding on the device: the block arrays above -> the
+ * bytes of one interleaved Huffman scan (ITU-T T.81, baseline sequential), and
+ * on the host the file header that goes in front of them (no reference
+ * counterpart).
+ *   input   d_y, d_cb, d_cr: exactly what hpdct_forward_blocks,
+ *           hpdct_forward_rgb_blocks and hpdct_forward_rgb_frame write; height
+ *           and width are those of the padded frame (Hp x Wp).  d_cb == d_cr ==
+ *           NULL: one component (grey), MCU = one block, sizes multiples of 8,
+ *           `sub` not read.  Else three components: sizes multiples of 8
+ *           (4:4:4, MCU = Y Cb Cr) or 16 (4:2:0, MCU = Y(0,0) Y(0,1) Y(1,0)
+ *           Y(1,1) Cb Cr, Y(dy,dx) = tile (2 my + dy, 2 mx + dx) of the Y plane).
+ *           MCUs in row-major order.  flags: 0 (zig-zag blocks) or
+ *           HPDCT_BLOCKS_NATURAL (permuted on load).
+ *   coding  the four typical tables of Annex K.3 (hpdct_huffman_table):
+ *           luminance DC / AC for Y, chrominance DC / AC for Cb and Cr.  DC
+ *           difference against the previous block of the same component,
+ *           magnitude category + extra bits (a negative v as v + 2^n - 1), AC
+ *           (run, size) symbols with ZRL for runs of 16 or more, EOB unless
+ *           coefficient 63 is non-zero; bits MSB first, every 0xFF byte
+ *           followed by 0x00.
+ *   restart restart_interval: 0 (the scan is one interval) or 1..65535 MCUs.
+ *           Each interval ends padded with 1 bits to a whole byte; every
+ *           interval but the last is followed by FF D0+(i mod 8), i its 0-based
+ *           index; the DC predictors are 0 at each interval's start.
+ *           d_interval_offsets (optional, intervals + 1 uint64): entry i is the
+ *           byte offset of interval i's first byte, entry `intervals` equals
+ *           info.bytes.  intervals = ceil(MCUs / restart_interval), or 1.
+ *   output  d_scan[0 .. info.bytes), any alignment; no byte at or beyond
+ *           d_scan + capacity is written, whatever the input.  If the scan does
+ *           not fit, info.truncated = 1, info.bytes = the size it needs and the
+ *           buffer holds nothing usable.  *d_info is written by the device.
+ *   range   a DC difference beyond +-2047 or an AC value beyond +-1023 has no
+ *           baseline code: each such coefficient is counted in
+ *           info.out_of_range and the bytes are then unspecified; the call is
+ *           still memory-safe and info.bytes <= hpdct_scan_bound.
+ *   bound   hpdct_scan_bound(blocks, intervals) = 415 * blocks + 4 * intervals
+ *           (-1 for a negative argument or an overflow): a block is at most
+ *           (11 + 11) + 63 * (16 + 10) = 1660 bits (longest DC code + 11 extra
+ *           bits, 63 times the longest AC code + 10), 207.5 bytes, twice that
+ *           when every byte is stuffed; an interval adds at most one padded,
+ *           stuffed byte (2) and its marker (2).
+ *   scratch no allocation, no process-wide state: d_workspace, at least
+ *           hpdct_scan_workspace_bytes(...) bytes (16 per interval at most; -1
+ *           for arguments the call would refuse), is all the call uses, so it
+ *           can be captured into a graph.  Three kernel launches in one chain,
+ *           asynchronous on `stream`.
+ *   speed   one wave codes one restart interval, so the call is parallel across
+ *           intervals only: tuned for one MCU row per interval;
+ *           restart_interval = 0 serialises the whole frame on one wave.
+ *   Every argument is checked before any device call.
+ *   HPDCT_ERROR_INVALID_VALUE: a null d_y, d_scan, d_info or d_workspace, only
+ *   one of d_cb / d_cr null; sizes that are not positive multiples of the MCU
+ *   or past the tile-count limit; an unknown subsampling (three components);
+ *   restart_interval outside 0..65535; a negative capacity; a block, workspace
+ *   or offsets pointer that is not 16-byte aligned, d_info not 8-byte aligned;
+ *   workspace_bytes too small; any two buffers overlapping.
+ *   HPDCT_ERROR_UNSUPPORTED: unknown flag bits. */
+typedef struct hpdct_scan_info {
+    uint64_t bytes;        /* length of the scan data; if truncated, the length it needs */
+    uint32_t truncated;    /* 1: bytes > capacity, the output holds nothing usable */
+    uint32_t out_of_range; /* number of coefficients baseline Huffman cannot code */
+} hpdct_scan_info;
+hpdct_status hpdct_encode_scan(const int16_t* d_y, const int16_t* d_cb, const int16_t* d_cr, int64_t height,
+                               int64_t width, hpdct_subsampling sub, int64_t restart_interval, unsigned flags,
+                               uint8_t* d_scan, int64_t capacity, hpdct_scan_info* d_info,
+                               uint64_t* d_interval_offsets, void* d_workspace, int64_t workspace_bytes,
+                               void* stream);
+int64_t hpdct_scan_bound(int64_t blocks, int64_t intervals); /* host: worst-case bytes */
+int64_t hpdct_scan_workspace_bytes(int64_t height, int64_t width, int components, hpdct_subsampling sub,
+                                   int64_t restart_interval); /* host */
+/* The file around the scan (host only): SOI, JFIF APP0, DQT (8-bit, zig-zag
+ * order), SOF0, DHT, DRI when restart_interval > 0, SOS (Ss = 0, Se = 63, Ah/Al =
+ * 0) into h_out; *bytes = the header's length (also when capacity is too small:
+ * HPDCT_ERROR_INVALID_VALUE, nothing written).  The caller appends the scan and
+ * FF D9.  height, width: the TRUE frame size, each 1..65535 (the scan holds the
+ * padded MCUs, which is what hpdct_forward_rgb_frame's edge replication
+ * produces).  components 1 (one DQT, two DHT tables) or 3 (two and four;
+ * sampling 1x1 for 4:4:4, 2x2 / 1x1 / 1x1 for 4:2:0; `sub` not read for 1).
+ * q_luma64 NULL: the library table; q_chroma64 NULL: the Annex K table (not
+ * read for 1 component); an entry that is not an integer in 1..255 returns
+ * HPDCT_ERROR_RANGE.
+ * A standard decoder inverts with the exact DCT, while this library's T is the
+ * HpApprDCT approximation: such a file decodes to an approximation of what
+ * hpdct_inverse_* gives for the same blocks (DESIGN.md 4.8 records how close).
+ * hpdct_huffman_table: bits16[l-1] = number of codes of length l, vals[0 ..
+ * *nvals) the symbols in code order (12 for a DC table, 162 for an AC table);
+ * an unknown kind sets *nvals = 0.  Any output pointer may be NULL. */
+hpdct_status hpdct_jpeg_header(uint8_t* h_out, int64_t capacity, int64_t* bytes, int64_t height, int64_t width,
+                               int components, hpdct_subsampling sub, const float* q_luma64,
+                               const float* q_chroma64, int64_t restart_interval);
+void hpdct_huffman_table(int kind /* 0 DC-luma, 1 AC-luma, 2 DC-chroma, 3 AC-chroma */, uint8_t* bits16, uint8_t* vals,
+                         int* nvals);
+
 /* Work mapping of the kernels (new; the reference has one fixed decomposition
  * per program).  Output is bit-identical in every mapping; only speed differs.
  *   AUTO   per frame: eight lanes per 8x8 tile ("octet") for frames below
