@@ -201,6 +201,19 @@ def _check(status: int) -> None:
         raise HpdctError(status, msg)
 
 
+def _bound(fn, args, keep=None):
+    """The zero-argument callable every bind_*() returns: the per-call host cost
+    is one ctypes call.  keep: host tables the library reads during the call,
+    alive as call.tables for as long as the callable is."""
+    def call():
+        st = fn(*args)
+        if st:
+            _check(st)
+    if keep is not None:
+        call.tables = keep
+    return call
+
+
 def version() -> str:
     return load_library().hpdct_version().decode()
 
@@ -301,6 +314,29 @@ def _hw(t, height, width):
     return h, w
 
 
+def _unit_hw(h: int, w: int, side: int):
+    if h <= 0 or w <= 0 or h % side or w % side:
+        raise HpdctError(1, f"height and width must be positive multiples of {side} (got {h}x{w})")
+    return h, w
+
+
+def _blocks_hw(t, height, width, what: str = "blocks"):
+    """height and width as given, or from a (H/8, W/8, 64) block tensor."""
+    if height is None or width is None:
+        if t.dim() != 3 or t.shape[-1] != 64:
+            raise HpdctError(1, f"pass height and width for {what} that are not (H/8, W/8, 64)")
+        height, width = 8 * t.shape[0], 8 * t.shape[1]
+    return int(height), int(width)
+
+
+def _disjoint(spans):
+    """spans: (first byte, one past the last, name) of every buffer of a launch."""
+    for i, (a0, a1, a) in enumerate(spans):
+        for b0, b1, b in spans[i + 1:]:
+            if a0 < b1 and b0 < a1:
+                raise HpdctError(1, f"the {a} and {b} buffers overlap")
+
+
 def _device_plane(t, what: str, device, need: int, dtypes=None):
     """The C-ABI cannot see buffer sizes: every device plane is checked here
     (CUDA, contiguous, on `device`, >= `need` elements, dtype allowed)."""
@@ -350,13 +386,8 @@ def forward(image, out=None, *, out_dtype=None, transform=None, quantise=True, w
     _device_plane(image, "image", None, 0)
     if out is None:
         out = torch.empty(image.shape, dtype=out_dtype or torch.float32, device=image.device)
-    h, w = _planes(image, out, "fwd", height, width)
-    flags = (0 if quantise else FLAG_NO_QUANT) | (FLAG_WRITEBACK_SHIFT if writeback_shift else 0) | \
-        (0 if level_shift else FLAG_NO_SHIFT) | (FLAG_ROW_FIRST if row_first else 0)
-    tptr = _transform_ptr(transform, image.device)
-    _check(load_library().hpdct_forward(ctypes.c_void_p(image.data_ptr()), _dtype_code(image),
-                                        ctypes.c_void_p(out.data_ptr()), _dtype_code(out), h, w, tptr,
-                                        flags, _stream_ptr(stream)))
+    bind("fwd", image, out, transform=transform, quantise=quantise, level_shift=level_shift,
+         writeback_shift=writeback_shift, row_first=row_first, stream=stream, height=height, width=width)()
     return out
 
 
@@ -368,13 +399,8 @@ def inverse(coef, out=None, *, out_dtype=None, transform=None, dequantise=True, 
     _device_plane(coef, "coefficients", None, 0)
     if out is None:
         out = torch.empty(coef.shape, dtype=out_dtype or torch.float32, device=coef.device)
-    h, w = _planes(coef, out, "inv", height, width)
-    flags = (0 if dequantise else FLAG_NO_QUANT) | (0 if level_shift else FLAG_NO_SHIFT) | \
-        (FLAG_ROW_FIRST if row_first else 0) | (FLAG_WRITEBACK_DEQUANT if writeback_dequant else 0)
-    tptr = _transform_ptr(transform, coef.device)
-    _check(load_library().hpdct_inverse(ctypes.c_void_p(coef.data_ptr()), _dtype_code(coef),
-                                        ctypes.c_void_p(out.data_ptr()), _dtype_code(out), h, w, tptr,
-                                        flags, _stream_ptr(stream)))
+    bind("inv", coef, out, transform=transform, quantise=dequantise, level_shift=level_shift, row_first=row_first,
+         writeback_dequant=writeback_dequant, stream=stream, height=height, width=width)()
     return out
 
 
@@ -391,14 +417,10 @@ def bind(direction: str, src, dst, *, transform=None, quantise=True, level_shift
     flags = (0 if quantise else FLAG_NO_QUANT) | (0 if level_shift else FLAG_NO_SHIFT) | \
         (FLAG_WRITEBACK_SHIFT if writeback_shift else 0) | (FLAG_ROW_FIRST if row_first else 0) | \
         (FLAG_WRITEBACK_DEQUANT if writeback_dequant else 0)
+    tptr = _transform_ptr(transform, src.device)
     args = (ctypes.c_void_p(src.data_ptr()), _dtype_code(src), ctypes.c_void_p(dst.data_ptr()), _dtype_code(dst),
-            h, w, _transform_ptr(transform, src.device), flags, _stream_ptr(stream))
-
-    def call():
-        st = fn(*args)
-        if st:
-            _check(st)
-    return call
+            h, w, tptr, flags, _stream_ptr(stream))
+    return _bound(fn, args)
 
 
 # ---------------------------------------------------------------------------
@@ -418,12 +440,6 @@ def _block_flags(order: str) -> int:
     return BLOCK_ORDERS[order]
 
 
-def _frame_hw(h: int, w: int):
-    if h <= 0 or w <= 0 or h % 8 or w % 8:
-        raise HpdctError(1, f"height and width must be positive multiples of 8 (got {h}x{w})")
-    return h, w
-
-
 def _block_planes(direction: str, src, dst, height, width):
     """Buffer checks of one block launch (the C-ABI sees raw pointers only);
     returns (image, blocks, h, w).  fwd: src the uint8 frame, dst the int16
@@ -431,15 +447,11 @@ def _block_planes(direction: str, src, dst, height, width):
     torch = _torch()
     if direction == "fwd":
         _device_plane(src, "image", None, 0, (torch.uint8,))
-        h, w = _frame_hw(*_hw(src, height, width))
+        h, w = _unit_hw(*_hw(src, height, width), 8)
         _device_plane(dst, "out", src.device, h * w, (torch.int16,))
         return src, dst, h, w
     _device_plane(src, "blocks", None, 0, (torch.int16,))
-    if height is None or width is None:
-        if src.dim() != 3 or src.shape[-1] != 64:
-            raise HpdctError(1, "pass height and width for blocks that are not (H/8, W/8, 64)")
-        height, width = 8 * src.shape[0], 8 * src.shape[1]
-    h, w = _frame_hw(int(height), int(width))
+    h, w = _unit_hw(*_blocks_hw(src, height, width), 8)
     if src.numel() < h * w:
         raise HpdctError(1, f"blocks hold {src.numel()} elements, a {h}x{w} frame needs {h * w}")
     _device_plane(dst, "out", src.device, h * w, (torch.float32, torch.uint8))
@@ -454,7 +466,7 @@ def forward_blocks(image, out=None, *, order: str = "zigzag", height=None, width
     torch = _torch()
     flags = _block_flags(order)
     _device_plane(image, "image", None, 0, (torch.uint8,))
-    h, w = _frame_hw(*_hw(image, height, width))
+    h, w = _unit_hw(*_hw(image, height, width), 8)
     if out is None:
         out = torch.empty((h // 8, w // 8, 64), dtype=torch.int16, device=image.device)
     _block_planes("fwd", image, out, h, w)
@@ -472,11 +484,7 @@ def inverse_blocks(blocks, out=None, *, out_dtype=None, order: str = "zigzag", h
     flags = _block_flags(order)
     _device_plane(blocks, "blocks", None, 0, (torch.int16,))
     if out is None:
-        if height is None or width is None:
-            if blocks.dim() != 3 or blocks.shape[-1] != 64:
-                raise HpdctError(1, "pass height and width for blocks that are not (H/8, W/8, 64)")
-            height, width = 8 * blocks.shape[0], 8 * blocks.shape[1]
-        h, w = _frame_hw(int(height), int(width))
+        h, w = _unit_hw(*_blocks_hw(blocks, height, width), 8)
         out = torch.empty((h, w), dtype=out_dtype or torch.float32, device=blocks.device)
     _, _, h, w = _block_planes("inv", blocks, out, height, width)
     _check(load_library().hpdct_inverse_blocks(ctypes.c_void_p(blocks.data_ptr()), ctypes.c_void_p(out.data_ptr()),
@@ -498,12 +506,7 @@ def bind_blocks(direction: str, src, dst, *, order: str = "zigzag", height=None,
         fn, args = lib.hpdct_forward_blocks, (ip, bp, h, w, flags, _stream_ptr(stream))
     else:
         fn, args = lib.hpdct_inverse_blocks, (bp, ip, _dtype_code(image), h, w, flags, _stream_ptr(stream))
-
-    def call():
-        st = fn(*args)
-        if st:
-            _check(st)
-    return call
+    return _bound(fn, args)
 
 
 # ---------------------------------------------------------------------------
@@ -542,10 +545,7 @@ def _rgb_hw(rgb, sub: int):
         raise HpdctError(1, "the RGB frame must be shaped (H, W, 3)")
     w = int(rgb.shape[-2])
     h = rgb.numel() // (3 * w) if w else 0
-    side = 16 if sub == 1 else 8
-    if h <= 0 or w <= 0 or h % side or w % side:
-        raise HpdctError(1, f"height and width must be positive multiples of {side} (got {h}x{w})")
-    return h, w
+    return _unit_hw(h, w, 16 if sub == 1 else 8)
 
 
 def _rgb_planes(rgb, y, cb, cr, h: int, w: int, sub: int):
@@ -557,12 +557,8 @@ def _rgb_planes(rgb, y, cb, cr, h: int, w: int, sub: int):
     ch, cw = (h // 2, w // 2) if sub == 1 else (h, w)
     for t, what, need in ((y, "y blocks", h * w), (cb, "cb blocks", ch * cw), (cr, "cr blocks", ch * cw)):
         _device_plane(t, what, rgb.device, need, (torch.int16,))
-    spans = [(t.data_ptr(), t.data_ptr() + n, what) for t, n, what in
-             ((rgb, 3 * h * w, "rgb"), (y, 2 * h * w, "y"), (cb, 2 * ch * cw, "cb"), (cr, 2 * ch * cw, "cr"))]
-    for i in range(4):
-        for j in range(i + 1, 4):
-            if spans[i][0] < spans[j][1] and spans[j][0] < spans[i][1]:
-                raise HpdctError(1, f"the {spans[i][2]} and {spans[j][2]} buffers overlap")
+    _disjoint([(t.data_ptr(), t.data_ptr() + n, what) for t, n, what in
+               ((rgb, 3 * h * w, "rgb"), (y, 2 * h * w, "y"), (cb, 2 * ch * cw, "cb"), (cr, 2 * ch * cw, "cr"))])
 
 
 def _rgb_block_shapes(h: int, w: int, sub: int):
@@ -574,13 +570,7 @@ def _rgb_call(fn, ptrs, h, w, sub, ql, qc, flags, stream):
     args = tuple(ctypes.c_void_p(p) for p in ptrs) + (
         h, w, sub, None if ql is None else ql.ctypes.data, None if qc is None else qc.ctypes.data, flags,
         _stream_ptr(stream))
-
-    def call():
-        st = fn(*args)
-        if st:
-            _check(st)
-    call.tables = (ql, qc)  # the host tables live as long as the callable
-    return call
+    return _bound(fn, args, keep=(ql, qc))
 
 
 def forward_rgb_blocks(rgb, *, subsampling: str = "420", q_luma=None, q_chroma=None, order: str = "zigzag",
@@ -606,15 +596,7 @@ def forward_rgb_blocks(rgb, *, subsampling: str = "420", q_luma=None, q_chroma=N
 
 
 def _rgb_inverse_hw(y, sub: int, height, width):
-    if height is None or width is None:
-        if y.dim() != 3 or y.shape[-1] != 64:
-            raise HpdctError(1, "pass height and width for y blocks that are not (H/8, W/8, 64)")
-        height, width = 8 * y.shape[0], 8 * y.shape[1]
-    h, w = int(height), int(width)
-    side = 16 if sub == 1 else 8
-    if h <= 0 or w <= 0 or h % side or w % side:
-        raise HpdctError(1, f"height and width must be positive multiples of {side} (got {h}x{w})")
-    return h, w
+    return _unit_hw(*_blocks_hw(y, height, width, "y blocks"), 16 if sub == 1 else 8)
 
 
 def inverse_rgb_blocks(y, cb, cr, *, subsampling: str, q_luma=None, q_chroma=None, order: str = "zigzag",
@@ -703,12 +685,8 @@ def _rgb_frame_blocks(rgb, extent: int, y, cb, cr, geometry):
     _, _, yb, cbk = geometry
     for t, what, need in ((y, "y blocks", 64 * yb), (cb, "cb blocks", 64 * cbk), (cr, "cr blocks", 64 * cbk)):
         _device_plane(t, what, rgb.device, need, (torch.int16,))
-    spans = [(t.data_ptr(), t.data_ptr() + n, what) for t, n, what in
-             ((rgb, extent, "rgb"), (y, 128 * yb, "y"), (cb, 128 * cbk, "cb"), (cr, 128 * cbk, "cr"))]
-    for i in range(4):
-        for j in range(i + 1, 4):
-            if spans[i][0] < spans[j][1] and spans[j][0] < spans[i][1]:
-                raise HpdctError(1, f"the {spans[i][2]} and {spans[j][2]} buffers overlap")
+    _disjoint([(t.data_ptr(), t.data_ptr() + n, what) for t, n, what in
+               ((rgb, extent, "rgb"), (y, 128 * yb, "y"), (cb, 128 * cbk, "cb"), (cr, 128 * cbk, "cr"))])
 
 
 def _rgb_frame_shapes(geometry, sub: int):
@@ -728,13 +706,7 @@ def _rgb_frame_call(direction, rgb, pitch, y, cb, cr, h, w, sub, ql, qc, flags, 
     else:
         fn = lib.hpdct_inverse_rgb_frame
         args = (vp(y.data_ptr()), vp(cb.data_ptr()), vp(cr.data_ptr()), vp(rgb.data_ptr()), pitch) + tail
-
-    def call():
-        st = fn(*args)
-        if st:
-            _check(st)
-    call.tables = (ql, qc)  # the host tables live as long as the callable
-    return call
+    return _bound(fn, args, keep=(ql, qc))
 
 
 def forward_rgb_frame(rgb, *, subsampling: str = "420", q_luma=None, q_chroma=None, order: str = "zigzag",
@@ -843,15 +815,9 @@ def _scan_planes(y, cb, cr, height, width, sub: int, restart_interval: int):
     _device_plane(y, "y blocks", None, 0, (torch.int16,))
     if (cb is None) != (cr is None):
         raise HpdctError(1, "cb and cr are both given or both None")
-    if height is None or width is None:
-        if y.dim() != 3 or y.shape[-1] != 64:
-            raise HpdctError(1, "pass height and width for y blocks that are not (H/8, W/8, 64)")
-        height, width = 8 * y.shape[0], 8 * y.shape[1]
-    h, w = int(height), int(width)
     components = 1 if cb is None else 3
     side = 16 if components == 3 and sub == 1 else 8
-    if h <= 0 or w <= 0 or h % side or w % side:
-        raise HpdctError(1, f"height and width must be positive multiples of {side} (got {h}x{w})")
+    h, w = _unit_hw(*_blocks_hw(y, height, width, "y blocks"), side)
     ri = int(restart_interval)
     if not 0 <= ri <= 65535:
         raise HpdctError(1, f"restart_interval must be 0..65535 (got {ri})")
@@ -892,13 +858,7 @@ def bind_scan(y, cb, cr, scan, info, offsets, workspace, *, height=None, width=N
             h, w, sub, int(restart_interval), flags, vp(scan.data_ptr()), cap, vp(info.data_ptr()),
             None if offsets is None else vp(offsets.data_ptr()), vp(workspace.data_ptr()), workspace.numel(),
             _stream_ptr(stream))
-    fn = load_library().hpdct_encode_scan
-
-    def call():
-        st = fn(*args)
-        if st:
-            _check(st)
-    return call
+    return _bound(load_library().hpdct_encode_scan, args)
 
 
 def scan_info(info) -> dict:
@@ -1033,13 +993,7 @@ def bind_roundtrip(image, coef, recon=None, sums_buf=None, *, stream=None, heigh
         raise HpdctError(1, "accumulate=True needs a sums buffer")
     args = _roundtrip_args(image, coef, recon, sums_buf, height, width, stream)
     lib = load_library()
-    fn = lib.hpdct_roundtrip_u8_accumulate if accumulate else lib.hpdct_roundtrip_u8
-
-    def call():
-        st = fn(*args)
-        if st:
-            _check(st)
-    return call
+    return _bound(lib.hpdct_roundtrip_u8_accumulate if accumulate else lib.hpdct_roundtrip_u8, args)
 
 
 def baseline_forward(kind: str, image, tmp, result, transform, stream=None) -> None:
@@ -1112,13 +1066,7 @@ def bind_frames(frames, outs, *, stream=None):
     n = len(frames)
     fp = (ctypes.c_void_p * n)(*[f.data_ptr() for f in frames])
     op = (ctypes.c_void_p * n)(*[o.data_ptr() for o in outs])
-    fn, args = load_library().hpdct_forward_frames, (fp, op, _dtype_code(outs[0]), n, h, w, _stream_ptr(stream))
-
-    def call():
-        st = fn(*args)
-        if st:
-            _check(st)
-    return call
+    return _bound(load_library().hpdct_forward_frames, (fp, op, _dtype_code(outs[0]), n, h, w, _stream_ptr(stream)))
 
 
 def _stream_lists(frames, outs):
@@ -1239,14 +1187,8 @@ def bind_floor_probe(kind: int, img=None, out=None, height: int = 0, width: int 
         _device_plane(img, "img", None, int(height) * int(width), (torch.uint8,))
         _device_plane(out, "out", img.device, int(height) * int(width), (torch.float32,))
         ip, op = ctypes.c_void_p(img.data_ptr()), ctypes.c_void_p(out.data_ptr())
-    fn = load_library().hpdct_floor_probe
-    args = (int(kind), ip, op, int(height), int(width), _stream_ptr(stream))
-
-    def call():
-        st = fn(*args)
-        if st:
-            _check(st)
-    return call
+    return _bound(load_library().hpdct_floor_probe,
+                  (int(kind), ip, op, int(height), int(width), _stream_ptr(stream)))
 
 
 def floor_probe(kind: int, img=None, out=None, height: int = 0, width: int = 0, stream=None) -> None:
@@ -1266,13 +1208,7 @@ def bind_copy_ceiling(src, out0, out1=None, *, cap_waves: int = 0, stream=None):
     args = (ctypes.c_void_p(src.data_ptr()), _dtype_code(src), ctypes.c_void_p(out0.data_ptr()), _dtype_code(out0),
             None if out1 is None else ctypes.c_void_p(out1.data_ptr()), F32 if out1 is None else _dtype_code(out1),
             n, int(cap_waves), _stream_ptr(stream))
-    fn = load_library().hpdct_copy_ceiling
-
-    def call():
-        st = fn(*args)
-        if st:
-            _check(st)
-    return call
+    return _bound(load_library().hpdct_copy_ceiling, args)
 
 
 def release_sums(sums_buf) -> None:

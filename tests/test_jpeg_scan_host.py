@@ -13,16 +13,15 @@
 import ctypes
 import io
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import decoder_blocks
+import host_programs
 import jpeg_scan as J
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_PKG = os.path.join(ROOT, "cuda-dct-idct_amd")
 S444, S420 = 0, 1
 
 
@@ -420,48 +419,14 @@ def test_scan_wrapper_checks(hp):
 
 def test_scan_policy_rows(tmp_path):
     """tests/tools/policy_scan_check.cpp: the coder's launches as hpdct_policy.hpp chooses them."""
-    exe = str(tmp_path / "policy_scan_check")
-    b = subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
-                        "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(_PKG, "csrc"),
-                        "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-g", "-O1",
-                        os.path.join(ROOT, "tests", "tools", "policy_scan_check.cpp"), "-o", exe],
-                       capture_output=True, text=True, timeout=300)
-    assert b.returncode == 0, b.stdout + b.stderr
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "policy_scan_check: ok" in r.stdout
+    host_programs.policy_check("policy_scan_check", tmp_path)
 
 
 # ---------------------------------------------------------------------------
 # the same validation paths and the header writer under ASan + UBSan
 # ---------------------------------------------------------------------------
-def _asan_mk(name):
-    """A variable of tests/tools/asan.mk, as make expands it."""
-    mk = os.path.join(ROOT, "tests", "tools", "asan.mk")
-    r = subprocess.run(["make", "-s", "-f", mk, "-f", "-", "print"], input="print:\n\t@echo $(%s)\n" % name,
-                       capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0, r.stdout + r.stderr
-    return r.stdout.split()
-
-
 def test_scan_validation_clean_under_asan_ubsan(tmp_path):
     """A stand-alone program (tests/tools/asan_scan_check.cpp, its own main) drives hpdct_encode_scan's refusals
     and hpdct_jpeg_header with hpdct_api.cpp compiled by g++ under tests/tools/asan.mk's ASan + UBSan flags and the
     library's kernel objects linked as they are.  CPU only: nothing is launched, nothing is loaded into Python."""
-    kobj = _asan_mk("KOBJ")
-    want = [line.split(":=")[1].split() for line in open(os.path.join(_PKG, "Makefile")) if line.startswith("KOBJ")][0]
-    assert len(kobj) == len(want) and any(o.endswith("hpdct_scan.o") for o in kobj), \
-        "library objects not built (__graft_entry__.build())"
-    exe = str(tmp_path / "asan_scan_check")
-    b = subprocess.run(["g++"] + _asan_mk("CXXF") +
-                       [os.path.join(ROOT, "tests", "tools", "asan_scan_check.cpp"),
-                        os.path.join(_PKG, "csrc", "hpdct_api.cpp")] + kobj +
-                       ["-o", exe, "-L/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib", "-lamdhip64", "-lpthread", "-lm"],
-                       capture_output=True, text=True, timeout=600)
-    assert b.returncode == 0, b.stdout + b.stderr
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120,
-                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:halt_on_error=1",
-                                UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1"))
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "asan_scan_check: ok" in r.stdout
-    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr
+    host_programs.sanitised_check("asan_scan_check", tmp_path, "hpdct_scan.o")

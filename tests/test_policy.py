@@ -7,23 +7,12 @@ with, no device and no library needed.
 """
 import os
 import shutil
-import subprocess
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PKG = os.path.join(ROOT, "cuda-dct-idct_amd")
+import host_programs
 
 
 def test_policy_table(tmp_path):
     # the only pin of the policy: a missing toolchain is a failure, not a skip
     assert shutil.which("g++") is not None, "g++ not found: the policy table cannot be checked"
     assert os.path.isdir("/opt/rocm/include"), "ROCm headers not found: the policy table cannot be checked"
-    exe = str(tmp_path / "policy_check")
-    b = subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
-                        "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(PKG, "csrc"),
-                        "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-g", "-O1",
-                        os.path.join(ROOT, "tests", "tools", "policy_check.cpp"), "-o", exe],
-                       capture_output=True, text=True, timeout=300)
-    assert b.returncode == 0, b.stdout + b.stderr
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "policy_check: ok" in r.stdout
+    host_programs.policy_check("policy_check", tmp_path)

@@ -10,11 +10,11 @@
 """
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_programs
 from test_host_validation import FakeDev
 from test_rgb_host import CHROMA
 
@@ -171,51 +171,14 @@ def test_frame_symbols_are_declared(hp):
 def test_rgb_frame_policy_table(tmp_path):
     """tests/tools/policy_rgb_frame_check.cpp: a whole-unit aligned call gets exactly the Choice of the existing
     policy rows, a ragged or unaligned one the clip variant with the padded grid's wave count."""
-    exe = str(tmp_path / "policy_rgb_frame_check")
-    b = subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
-                        "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "cuda-dct-idct_amd", "csrc"),
-                        "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-g", "-O1",
-                        os.path.join(ROOT, "tests", "tools", "policy_rgb_frame_check.cpp"), "-o", exe],
-                       capture_output=True, text=True, timeout=300)
-    assert b.returncode == 0, b.stdout + b.stderr
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "policy_rgb_frame_check: ok" in r.stdout
-
-
-_PKG = os.path.join(ROOT, "cuda-dct-idct_amd")
-
-
-def _asan_mk(name):
-    """A variable of tests/tools/asan.mk, as make expands it."""
-    mk = os.path.join(ROOT, "tests", "tools", "asan.mk")
-    r = subprocess.run(["make", "-s", "-f", mk, "-f", "-", "print"], input="print:\n\t@echo $(%s)\n" % name,
-                       capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0, r.stdout + r.stderr
-    return r.stdout.split()
+    host_programs.policy_check("policy_rgb_frame_check", tmp_path)
 
 
 def test_frame_validation_clean_under_asan_ubsan(tmp_path):
     """A stand-alone program (tests/tools/asan_rgb_frame_check.cpp, its own main) drives the validation paths
     with hpdct_api.cpp compiled by g++ under tests/tools/asan.mk's ASan + UBSan flags and the library's kernel
     objects linked as they are.  CPU only: nothing is launched, nothing is loaded into Python."""
-    kobj = _asan_mk("KOBJ")
-    want = [line.split(":=")[1].split() for line in open(os.path.join(_PKG, "Makefile")) if line.startswith("KOBJ")][0]
-    assert len(kobj) == len(want) and any(o.endswith("hpdct_rgb_fwd420_clip.o") for o in kobj), \
-        "library objects not built (__graft_entry__.build())"
-    exe = str(tmp_path / "asan_rgb_frame_check")
-    b = subprocess.run(["g++"] + _asan_mk("CXXF") +
-                       [os.path.join(ROOT, "tests", "tools", "asan_rgb_frame_check.cpp"),
-                        os.path.join(_PKG, "csrc", "hpdct_api.cpp")] + kobj +
-                       ["-o", exe, "-L/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib", "-lamdhip64", "-lpthread", "-lm"],
-                       capture_output=True, text=True, timeout=600)
-    assert b.returncode == 0, b.stdout + b.stderr
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120,
-                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:halt_on_error=1",
-                                UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1"))
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "asan_rgb_frame_check: ok" in r.stdout
-    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr
+    host_programs.sanitised_check("asan_rgb_frame_check", tmp_path, "hpdct_rgb_fwd420_clip.o")
 
 
 class _View(FakeDev):

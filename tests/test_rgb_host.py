@@ -10,11 +10,11 @@
 """
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_programs
 from test_host_validation import FakeDev
 
 RGB, Y, CB, CR = 1 << 20, 1 << 30, 1 << 31, 1 << 32  # far apart, 16-byte aligned, never dereferenced
@@ -129,21 +129,10 @@ def test_rgb_symbols_are_declared(hp):
 def test_rgb_policy_table(tmp_path):
     """policy::forward_rgb / inverse_rgb pinned on the CPU (tests/tools/policy_rgb_check.cpp): the staged
     forward, the three quotient pairs, the grid of one wave per 64 units."""
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    exe = str(tmp_path / "policy_rgb_check")
-    b = subprocess.run(["g++", "-std=c++17", "-Wall", "-Werror", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
-                        "-I" + os.path.join(root, "include"), "-I" + os.path.join(root, "cuda-dct-idct_amd", "csrc"),
-                        "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-g", "-O1",
-                        os.path.join(root, "tests", "tools", "policy_rgb_check.cpp"), "-o", exe],
-                       capture_output=True, text=True, timeout=300)
-    assert b.returncode == 0, b.stdout + b.stderr
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "policy_rgb_check: ok" in r.stdout
+    host_programs.policy_check("policy_rgb_check", tmp_path)
 
 
-_PKG = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "cuda-dct-idct_amd")
-_KOBJ = os.path.join(_PKG, "build", "hpdct_rgb_inv.o")
+_KOBJ = os.path.join(host_programs.PKG, "build", "hpdct_rgb_inv.o")
 
 
 @pytest.mark.skipif(not os.path.exists(_KOBJ), reason="library objects not built (__graft_entry__.build())")
@@ -151,25 +140,7 @@ def test_rgb_validation_clean_under_asan_ubsan(tmp_path):
     """A stand-alone program (tests/tools/asan_rgb_check.cpp) drives the new validation paths with
     hpdct_api.cpp compiled by g++ under ASan + UBSan and the library's kernel objects linked as they are
     (the Makefile's KOBJ line).  CPU only: nothing is launched."""
-    root = os.path.dirname(_PKG)
-    kobj = [os.path.join(_PKG, o) for line in open(os.path.join(_PKG, "Makefile")) if line.startswith("KOBJ")
-            for o in line.split(":=")[1].split()]
-    assert _KOBJ in kobj and all(os.path.exists(o) for o in kobj)
-    san = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer", "-g", "-O1"]
-    cxx = ["g++", "-std=c++17", "-ffp-contract=off", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
-           "-I" + os.path.join(root, "include"), "-I" + os.path.join(_PKG, "csrc"), "-I" + os.path.join(_PKG, "build")]
-    exe = str(tmp_path / "asan_rgb_check")
-    b = subprocess.run(cxx + san + [os.path.join(root, "tests", "tools", "asan_rgb_check.cpp"),
-                                    os.path.join(_PKG, "csrc", "hpdct_api.cpp")] + kobj +
-                       ["-o", exe, "-L/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib", "-lamdhip64", "-lpthread", "-lm"],
-                       capture_output=True, text=True, timeout=600)
-    assert b.returncode == 0, b.stdout + b.stderr
-    r = subprocess.run([exe], capture_output=True, text=True, timeout=120,
-                       env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:halt_on_error=1",
-                                UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1"))
-    assert r.returncode == 0, r.stdout + r.stderr
-    assert "asan_rgb_check: ok" in r.stdout
-    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr
+    host_programs.sanitised_check("asan_rgb_check", tmp_path, "hpdct_rgb_inv.o")
 
 
 class _Dev(FakeDev):

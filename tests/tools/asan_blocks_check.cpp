@@ -46,12 +46,33 @@ int main() {
     expect("inv overlap", hpdct_inverse_blocks(B, at(reinterpret_cast<uint8_t*>(B), 64), HPDCT_U8, 8, 8, 0, nullptr), 1,
            "overlap");
     expect("inv flag 0x80", hpdct_inverse_blocks(B, A, HPDCT_U8, 8, 8, HPDCT_BLOCKS_NATURAL | 0x80u, nullptr), 2);
+    // the shared overlap check, 8x8: 64 bytes of uint8 pixels (8-byte units), 128 of blocks (16-byte units).
+    // The later buffer starts one unit before the earlier one's end, either way round; TOP's extent would wrap.
+    const auto A16 = reinterpret_cast<int16_t*>(A);
+    const auto B8 = reinterpret_cast<uint8_t*>(B);
+    const uintptr_t top = (~uintptr_t(0) - 50) & ~uintptr_t(15);
+    expect("fwd blocks at image end - 16", hpdct_forward_blocks(A, at(A16, 48), 8, 8, 0, nullptr), 1, "overlap");
+    expect("fwd image at blocks end - 8", hpdct_forward_blocks(at(B8, 120), B, 8, 8, 0, nullptr), 1, "overlap");
+    expect("fwd image wraps", hpdct_forward_blocks(reinterpret_cast<uint8_t*>(top), B, 8, 8, 0, nullptr), 1, "wrap");
+    expect("fwd blocks wrap", hpdct_forward_blocks(A, reinterpret_cast<int16_t*>(top), 8, 8, 0, nullptr), 1, "wrap");
+    expect("inv pixels at blocks end - 8", hpdct_inverse_blocks(B, at(B8, 120), HPDCT_U8, 8, 8, 0, nullptr), 1,
+           "overlap");
+    expect("inv blocks at pixels end - 16", hpdct_inverse_blocks(at(A16, 48), A, HPDCT_U8, 8, 8, 0, nullptr), 1,
+           "overlap");
+    expect("inv pixels wrap", hpdct_inverse_blocks(B, reinterpret_cast<uint8_t*>(top), HPDCT_F32, 8, 8, 0, nullptr), 1,
+           "wrap");
 
     // the range rule: 1/64 everywhere can give |q| = 65536
     float q[64];
     for (float& v : q) v = 1.0f / 64.0f;
     expect("set 1/64 table", hpdct_set_quant_table(q), 0);
     expect("fwd range", hpdct_forward_blocks(A, B, 8, 8, 0, nullptr), 3, "int16");
+    // blocks right behind the image (and the image right behind the blocks) are no overlap: under a table of
+    // 0.001 the call gets as far as the range rule
+    for (float& v : q) v = 0.001f;
+    expect("set 0.001 table", hpdct_set_quant_table(q), 0);
+    expect("fwd blocks at image end", hpdct_forward_blocks(A, at(A16, 64), 8, 8, 0, nullptr), 3, "int16");
+    expect("fwd image at blocks end", hpdct_forward_blocks(at(B8, 128), B, 8, 8, 0, nullptr), 3, "int16");
     expect("restore table", hpdct_set_quant_table(nullptr), 0);
     // a huge finite table is legal (the inverses take their full-chain kernels under it): the skip criterion
     // is computed when the table is set, and a call is still judged by its arguments first

@@ -197,6 +197,47 @@ static void validation_paths() {
     CHECK(hpdct_stream_forward(frames, outs, 0, 64, 64, HPDCT_F32, 2, &ms) == HPDCT_SUCCESS);
 }
 
+// The overlap check hpdct_forward, hpdct_inverse and the round trip share, on
+// 8x8 frames.  Every call is refused before a launch: two buffers that only
+// touch are shown by a later refusal (the range rule under a table of 0.001).
+static void span_paths() {
+    auto refused = [](int st, int want, const char* text) {
+        return st == want && strstr(hpdct_last_error_string(), text) != nullptr;
+    };
+    char* a = (char*)((uintptr_t)1 << 20);
+    char* top = (char*)((~(uintptr_t)0 - 50) & ~(uintptr_t)15);  // any extent from here wraps
+    const int inval = HPDCT_ERROR_INVALID_VALUE;
+    // uint8 -> int8: 64 bytes each, 8-byte units
+    CHECK(refused(hpdct_forward(a, HPDCT_U8, a + 56, HPDCT_I8, 8, 8, nullptr, 0, nullptr), inval, "overlap"));
+    CHECK(refused(hpdct_forward(a + 56, HPDCT_U8, a, HPDCT_I8, 8, 8, nullptr, 0, nullptr), inval, "overlap"));
+    CHECK(refused(hpdct_forward(top, HPDCT_U8, a, HPDCT_I8, 8, 8, nullptr, 0, nullptr), inval, "wrap"));
+    CHECK(refused(hpdct_forward(a, HPDCT_U8, top, HPDCT_I8, 8, 8, nullptr, 0, nullptr), inval, "wrap"));
+    float fine[64];
+    for (float& v : fine) v = 0.001f;
+    CHECK(hpdct_set_quant_table(fine) == HPDCT_SUCCESS);
+    CHECK(refused(hpdct_forward(a, HPDCT_U8, a + 64, HPDCT_I8, 8, 8, nullptr, 0, nullptr), HPDCT_ERROR_RANGE, "127"));
+    CHECK(refused(hpdct_forward(a + 64, HPDCT_U8, a, HPDCT_I8, 8, 8, nullptr, 0, nullptr), HPDCT_ERROR_RANGE, "127"));
+    CHECK(hpdct_set_quant_table(nullptr) == HPDCT_SUCCESS);
+    // fp32 -> fp32: 256 bytes each, 16-byte units
+    CHECK(refused(hpdct_inverse(a, HPDCT_F32, a + 240, HPDCT_F32, 8, 8, nullptr, 0, nullptr), inval, "overlap"));
+    CHECK(refused(hpdct_inverse(a + 240, HPDCT_F32, a, HPDCT_F32, 8, 8, nullptr, 0, nullptr), inval, "overlap"));
+    CHECK(refused(hpdct_inverse(a, HPDCT_F32, top, HPDCT_F32, 8, 8, nullptr, 0, nullptr), inval, "wrap"));
+    // the round trip: image 64 bytes, coefficients 256, uint8 reconstruction 64, sums 24
+    auto rt = [](void* img, void* coef, void* recon, void* sums) {
+        return hpdct_roundtrip_u8((uint8_t*)img, (float*)coef, recon, HPDCT_U8, (hpdct_roundtrip_sums*)sums, 8, 8,
+                                  nullptr);
+    };
+    char* b = (char*)((uintptr_t)1 << 30);
+    char* c = (char*)((uintptr_t)1 << 31);
+    char* s = (char*)((uintptr_t)1 << 32);
+    CHECK(refused(rt(a, a + 48, c, s), inval, "overlap"));
+    CHECK(refused(rt(b + 248, b, c, s), inval, "overlap"));
+    CHECK(refused(rt(a, b, top, s), inval, "wrap"));
+    // buffers left out are skipped, the live ones still compared
+    CHECK(refused(rt(a, b, nullptr, a), inval, "overlap"));
+    CHECK(refused(rt(a, a + 48, nullptr, nullptr), inval, "overlap"));
+}
+
 static void oracle_paths() {
     float T[64], Q[64];
     oracle_default_transform(T);
@@ -255,6 +296,7 @@ int main(int argc, char** argv) {
     host_helpers();
     quant_table_threads();
     validation_paths();
+    span_paths();
     oracle_paths();
     image_io_paths(dir);
     printf("asan_host_check: %s (%d failed checks)\n", g_fail ? "FAIL" : "ok", g_fail);

@@ -66,6 +66,14 @@ int main() {
     expect("fwd cb = cr", fwd(RGB, Y, CB, CB, 16, 16, S420, nullptr, nullptr, 0), 1, "overlap");
     expect("fwd cr in cb 444", fwd(RGB, Y, CB, at(CB, 128), 16, 16, S444, nullptr, nullptr, 0), 1, "overlap");
     expect("fwd cb in y", fwd(RGB, Y, at(Y, 496), CR, 16, 16, S420, nullptr, nullptr, 0), 1, "overlap");
+    // the other way round: rgb starts one 16-byte unit before y's end; and a buffer whose extent would wrap
+    const uintptr_t top = (~uintptr_t(0) - 50) & ~uintptr_t(15);
+    expect("fwd rgb in y", fwd(at(reinterpret_cast<uint8_t*>(Y), 496), Y, CB, CR, 16, 16, S420, nullptr, nullptr, 0), 1,
+           "overlap");
+    expect("fwd rgb wraps", fwd(reinterpret_cast<uint8_t*>(top), Y, CB, CR, 16, 16, S420, nullptr, nullptr, 0), 1,
+           "wrap");
+    expect("fwd cr wraps", fwd(RGB, Y, CB, reinterpret_cast<int16_t*>(top), 16, 16, S420, nullptr, nullptr, 0), 1,
+           "wrap");
     expect("inv null", inv(Y, CB, CR, nullptr, 16, 16, S420, nullptr, nullptr, 0), 1, "null");
     expect("inv 8x8 420", inv(Y, CB, CR, RGB, 8, 8, S420, nullptr, nullptr, 0), 1, "multiples of 16");
     expect("inv enum 7", inv(Y, CB, CR, RGB, 16, 16, 7, nullptr, nullptr, 0), 1, "subsampling");
@@ -98,6 +106,14 @@ int main() {
     // the library-owned luma table is under the same rule
     expect("set 1/64 table", hpdct_set_quant_table(bad.get()), 0);
     expect("fwd range library table", fwd(RGB, Y, CB, CR, 16, 16, S420, nullptr, nullptr, 0), 3, "luma");
+    // y right behind the 768 bytes of rgb, and rgb right behind the 512 of y, are no overlap: under a library
+    // table of 0.001 the call gets as far as the range rule
+    for (int i = 0; i < 64; ++i) bad[i] = 0.001f;
+    expect("set 0.001 table", hpdct_set_quant_table(bad.get()), 0);
+    expect("fwd y at rgb end", fwd(RGB, reinterpret_cast<int16_t*>(at(RGB, 768)), CB, CR, 16, 16, S420, nullptr,
+                                   nullptr, 0), 3, "luma");
+    expect("fwd rgb at y end", fwd(at(reinterpret_cast<uint8_t*>(Y), 512), Y, CB, CR, 16, 16, S420, nullptr, nullptr, 0),
+           3, "luma");
     expect("restore table", hpdct_set_quant_table(nullptr), 0);
 
     if (g_bad != 0) {
