@@ -349,7 +349,8 @@ inline Choice inverse_rgb(const RgbCall& c) {
 
 // The entropy coder (hpdct_scan.hpp): its measure and emit launches run one
 // wave per restart interval in one-wave workgroups, no residency cap (a wave
-// holds 24 KiB of LDS: its bit buffer and its staged blocks); beyond
+// holds 37,480 bytes of LDS: its tables 2,176, its staged blocks 8,448, its
+// lanes' own words 13,568 and its bit buffer 13,288); beyond
 // kScanMaxWgs intervals a workgroup takes every kScanMaxWgs-th one.  The
 // offsets launch is one 1024-thread workgroup.  hpdct_set_mapping is not read.
 struct ScanCall {

@@ -13,6 +13,9 @@ int main() {
     auto expect = [&](const char* what, bool ok) {
         if (!ok) ++bad, std::printf("MISMATCH %s\n", what);
     };
+    // tests/test_gpu_scan_limits.py::test_more_intervals_than_workgroups codes 1025 x 1025 intervals, 2049 past
+    // this cap, to reach the coding kernel's second turn: a larger cap needs a larger frame there
+    expect("kScanMaxWgs", kScanMaxWgs == (1u << 20));
     for (uint32_t n : {1u, 2u, 512u, 1024u, kScanMaxWgs - 1u, kScanMaxWgs, kScanMaxWgs + 1u, 0xffffffffu})
         for (int natural = 0; natural < 2; ++natural)
             for (int emit = 0; emit < 2; ++emit) {
