@@ -78,6 +78,19 @@ enum : unsigned {
     kScanEmit = 1u << 28,     // scan_code_kernel: the emit launch (clear: the measure launch)
     kScanOffsets = 1u << 29,  // scan_offsets_kernel
 };
+// the entropy decoder's own variant bits (hpdct_unscan.hpp; its decode kernel also reads kScanNatural:
+// permuted on store)
+enum : unsigned {
+    kUnscanLanes16 = 1u << 20,  // unscan_decode_kernel: 16, 4 or 1 lanes of each wave take an interval
+    kUnscanLanes4 = 1u << 21,   // (none of the three: all 64)
+    kUnscanLanes1 = 1u << 22,
+    kUnscanCount = 1u << 23,    // unscan_locate_kernel: the counting pass (with kUnscanPlace: the placing pass)
+    kUnscanPlace = 1u << 24,
+    kUnscanRank = 1u << 28,     // unscan_rank_kernel
+};
+constexpr uint32_t unscan_lanes_of(unsigned var) {
+    return (var & kUnscanLanes16) ? 16u : (var & kUnscanLanes4) ? 4u : (var & kUnscanLanes1) ? 1u : 64u;
+}
 // Bits only the product kernels give a meaning to: the tools' A/B variant
 // bits must stay clear of them (static_assert in tools/kbench_variants.hpp).
 constexpr unsigned kProductOnlyVarBits = kVarFastDivChecked | kVarJpegQ;

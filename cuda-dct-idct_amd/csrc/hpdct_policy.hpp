@@ -16,7 +16,8 @@ namespace policy {
 // kBlocks: fdct_blocks_kernel / idct_blocks_kernel (hpdct_blocks.hpp)
 // kRgb: fdct_rgb_kernel / idct_rgb_kernel (hpdct_rgb.hpp)
 // kScan: scan_code_kernel / scan_offsets_kernel (hpdct_scan.hpp)
-enum class Family { kTile, kOctet, kDuo, kDuoFwdU8, kRowFirstDuo, kRtDuo, kRtTile, kBlocks, kRgb, kScan };
+// kUnscan: unscan_locate_kernel / unscan_rank_kernel / unscan_decode_kernel (hpdct_unscan.hpp)
+enum class Family { kTile, kOctet, kDuo, kDuoFwdU8, kRowFirstDuo, kRtDuo, kRtTile, kBlocks, kRgb, kScan, kUnscan };
 enum class Elem { kU8, kI8, kF32 };
 
 // var: the kernel's kVar; kDuoFwdU8 and kRt* carry their quotient and straddle bits there
@@ -363,6 +364,51 @@ inline Choice scan_code(const ScanCall& c, bool emit) {
             c.intervals < kScanMaxWgs ? c.intervals : kScanMaxWgs, 1u};
 }
 inline Choice scan_offsets() { return {Family::kScan, with_block<1024>(kScanOffsets), 1024u, 0u, 1u, 1u}; }
+
+// The entropy decoder (hpdct_unscan.hpp).  Huffman decoding is serial inside a
+// restart interval: one LANE walks one interval, in one-wave workgroups (the
+// tables and a lane's block row are 3,488 bytes of LDS with one lane, 11,792
+// with 64).  A lane's walk is a chain of dependent instructions, and lanes of
+// one wave that sit in different branches of the walk run one after the other,
+// so few lanes per wave are fastest while every wave is resident at once (the
+// device holds 256 CUs x 32 = kUnscanMaxWgs one-wave workgroups), and many
+// lanes per wave once the waves would queue.  Measured at 8192^2 grey, noise /
+// smooth, offsets given, us (tools/unscan_probe.py against builds with the rows
+// moved, profiles/r11/unscan_policy_ab.log):
+//    16,384 intervals:  1 lane 8,109 / 446   4 lanes 2,878 / 209   16 lanes 3,299 / 204
+//    32,768:            4 lanes 2,549 / 169  16 lanes 1,588 / 105
+//    65,536:           16 lanes   954 / 69   64 lanes 1,113 / 69
+//   131,072:            4 lanes 2,568 / 156  16 lanes   834 / 65   64 lanes 578 / 58
+// Hence 1 lane up to kUnscanMaxWgs intervals (an 8192^2 frame at one MCU row
+// per interval has 1,024), 4 up to 16,384, 16 up to 65,536, all 64 beyond;
+// beyond 64 * kUnscanMaxWgs intervals a workgroup takes every kUnscanMaxWgs-th
+// group of 64.  The marker search runs one wave per 4096-byte chunk in
+// 256-thread workgroups under the same grid cap, its ranks in one 1024-thread
+// workgroup.  hpdct_set_mapping is not read.
+struct UnscanCall {
+    uint32_t intervals = 1;
+    bool natural = false;
+};
+constexpr uint32_t kUnscanMaxWgs = 8192;
+constexpr uint32_t kUnscanChunkBytes = 4096;
+constexpr uint32_t kUnscanLanes4Max = 16384, kUnscanLanes16Max = 65536;
+constexpr uint32_t unscan_lanes(uint32_t intervals) {
+    return intervals <= kUnscanMaxWgs ? 1u : intervals <= kUnscanLanes4Max ? 4u : intervals <= kUnscanLanes16Max ? 16u : 64u;
+}
+inline Choice unscan_decode(const UnscanCall& c) {
+    const uint32_t lanes = unscan_lanes(c.intervals);
+    const uint32_t wgs = c.intervals / lanes + (c.intervals % lanes != 0u);
+    const unsigned bit = lanes == 16u ? kUnscanLanes16 : lanes == 4u ? kUnscanLanes4 : lanes == 1u ? kUnscanLanes1 : 0u;
+    return {Family::kUnscan, with_block<64>((c.natural ? kScanNatural : 0u) | bit), 64u, 0u,
+            wgs < kUnscanMaxWgs ? wgs : kUnscanMaxWgs, 1u};
+}
+// chunks: ceil(scan bytes / kUnscanChunkBytes), at least 1
+inline Choice unscan_locate(uint64_t chunks, bool place) {
+    const uint64_t wgs = (chunks + 3u) / 4u;
+    return {Family::kUnscan, with_block<256>(kUnscanCount | (place ? kUnscanPlace : 0u)), 256u, 0u,
+            wgs < kUnscanMaxWgs ? static_cast<uint32_t>(wgs) : kUnscanMaxWgs, 1u};
+}
+inline Choice unscan_rank() { return {Family::kUnscan, with_block<1024>(kUnscanRank), 1024u, 0u, 1u, 1u}; }
 
 // launch_roundtrip.  The two-lanes-per-tile round trip (hpdct_rt_duo.hpp) for
 // the verified quotient (qmode 1 or 2) with any reconstruction, when its sums

@@ -60,6 +60,7 @@ C_SYMBOLS = [
     "hpdct_rgb_frame_geometry", "hpdct_forward_rgb_frame", "hpdct_inverse_rgb_frame",
     "hpdct_encode_scan", "hpdct_scan_bound", "hpdct_scan_workspace_bytes", "hpdct_jpeg_header",
     "hpdct_huffman_table",
+    "hpdct_decode_scan", "hpdct_decode_workspace_bytes", "hpdct_jpeg_parse",
 ]
 MAPPINGS = {"auto": 0, "tile": 1, "octet": 2, "duo": 3}
 BASELINES = {"reference_3pass": 0, "fastappr_3pass": 1}
@@ -146,6 +147,13 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.hpdct_jpeg_header.restype = ctypes.c_int
     lib.hpdct_huffman_table.argtypes = [ctypes.c_int, vp, vp, vp]
     lib.hpdct_huffman_table.restype = None
+    lib.hpdct_decode_scan.argtypes = [vp, i64, vp, vp, vp, vp, i64, i64, ctypes.c_int, i64, ctypes.c_uint, vp, vp, vp,
+                                      i64, vp]
+    lib.hpdct_decode_scan.restype = ctypes.c_int
+    lib.hpdct_decode_workspace_bytes.argtypes = [i64, i64, ctypes.c_int, ctypes.c_int, i64, i64]
+    lib.hpdct_decode_workspace_bytes.restype = i64
+    lib.hpdct_jpeg_parse.argtypes = [vp, i64, vp]
+    lib.hpdct_jpeg_parse.restype = ctypes.c_int
     lib.hpdct_status_string.restype = ctypes.c_char_p
     lib.hpdct_status_string.argtypes = [ctypes.c_int]
     lib.hpdct_last_error_string.restype = ctypes.c_char_p
@@ -926,6 +934,177 @@ def jpeg_encode(image, *, subsampling: str = "420", q_luma=None, q_chroma=None, 
         raise HpdctError(3, f"{info['out_of_range']} coefficients are beyond baseline JPEG's range "
                             "(DC difference +-2047, AC +-1023): use a coarser quant table")
     return head + scan.cpu().numpy().tobytes() + b"\xff\xd9"
+
+
+# ---------------------------------------------------------------------------
+# Baseline-JPEG entropy decoding (hpdct_decode_scan) and the file's header
+# ---------------------------------------------------------------------------
+DECODE_STATUS = ["OK", "RANGE", "MARKER", "END", "CODE", "INDEX", "DC", "TAIL", "MISSING"]
+
+
+class _JpegLayout(ctypes.Structure):  # hpdct_jpeg_layout
+    _fields_ = [("height", ctypes.c_int64), ("width", ctypes.c_int64), ("components", ctypes.c_int),
+                ("sub", ctypes.c_int), ("restart_interval", ctypes.c_int64), ("scan_offset", ctypes.c_int64),
+                ("scan_bytes", ctypes.c_int64), ("q_luma", ctypes.c_float * 64), ("q_chroma", ctypes.c_float * 64)]
+
+
+def jpeg_parse(data) -> dict:
+    """SOI .. SOS of a baseline file (hpdct_jpeg_parse, host only): {"height",
+    "width" (the TRUE frame size), "components", "subsampling", "restart_interval",
+    "scan_offset", "scan_bytes", "q_luma", "q_chroma" (8x8 float32, row-major;
+    q_chroma None for one component)}.  HpdctError status 2 names why a file is
+    not one decode_scan decodes, status 1 a truncated or malformed file."""
+    buf = np.frombuffer(bytes(data), np.uint8)
+    lay = _JpegLayout()
+    _check(load_library().hpdct_jpeg_parse(buf.ctypes.data if buf.size else ctypes.addressof(lay), buf.size,
+                                           ctypes.addressof(lay)))
+    names = {v: k for k, v in SUBSAMPLINGS.items()}
+    return {"height": lay.height, "width": lay.width, "components": lay.components, "subsampling": names[lay.sub],
+            "restart_interval": lay.restart_interval, "scan_offset": lay.scan_offset, "scan_bytes": lay.scan_bytes,
+            "q_luma": np.array(lay.q_luma, np.float32).reshape(8, 8),
+            "q_chroma": np.array(lay.q_chroma, np.float32).reshape(8, 8) if lay.components == 3 else None}
+
+
+def _decode_geometry(height, width, components, sub: int, restart_interval):
+    """(h, w, components, side, nmcu, intervals) of a scan of the padded frame h x w."""
+    components, ri = int(components), int(restart_interval)
+    if components not in (1, 3):
+        raise HpdctError(1, "components must be 1 or 3")
+    side = 16 if components == 3 and sub == 1 else 8
+    h, w = _unit_hw(int(height), int(width), side)
+    if not 0 <= ri <= 65535:
+        raise HpdctError(1, f"restart_interval must be 0..65535 (got {ri})")
+    nmcu = (h // side) * (w // side)
+    return h, w, components, side, nmcu, 1 if ri == 0 else -(-nmcu // ri)
+
+
+def decode_workspace_bytes(height, width, *, components=1, subsampling="420", restart_interval=0, scan_bytes=0) -> int:
+    """hpdct_decode_workspace_bytes: 8 bytes per interval and per 4096 bytes of scan."""
+    n = int(load_library().hpdct_decode_workspace_bytes(int(height), int(width), int(components),
+                                                        _subsampling(subsampling), int(restart_interval),
+                                                        int(scan_bytes)))
+    if n < 0:
+        _check(1)
+    return n
+
+
+def bind_decode_scan(scan, offsets, y, cb, cr, info, status, workspace, *, height=None, width=None,
+                     subsampling: str = "420", restart_interval: int = 0, order: str = "zigzag", stream=None):
+    """Pre-resolved hpdct_decode_scan launch on the given buffers: a
+    zero-argument callable like the other bind_* functions (two kernel launches
+    with offsets, four without, no allocation: it can be captured into a graph).
+    scan: uint8, all of it is the scan; offsets: None (the markers are located)
+    or intervals + 1 int64; y, cb, cr: int16 block arrays to fill (cb = cr = None:
+    grey); info: 16 bytes (two int64); status: None or `intervals` int64;
+    workspace: uint8."""
+    torch = _torch()
+    sub, flags = _subsampling(subsampling), _block_flags(order)
+    _device_plane(y, "y blocks", None, 0, (torch.int16,))
+    if (cb is None) != (cr is None):
+        raise HpdctError(1, "cb and cr are both given or both None")
+    h, w = _blocks_hw(y, height, width, "y blocks")
+    h, w, components, side, nmcu, intervals = _decode_geometry(h, w, 1 if cb is None else 3, sub, restart_interval)
+    _device_plane(scan, "scan", y.device, 0, (torch.uint8,))
+    _device_plane(y, "y blocks", None, h * w, (torch.int16,))
+    if components == 3:
+        for t, what in ((cb, "cb blocks"), (cr, "cr blocks")):
+            _device_plane(t, what, y.device, 64 * nmcu, (torch.int16,))
+    _device_plane(info, "info", y.device, 2, (torch.int64,))
+    if offsets is not None:
+        _device_plane(offsets, "offsets", y.device, intervals + 1, (torch.int64,))
+    if status is not None:
+        _device_plane(status, "status", y.device, intervals, (torch.int64,))
+    ws = decode_workspace_bytes(h, w, components=components, subsampling=subsampling,
+                                restart_interval=restart_interval, scan_bytes=scan.numel())
+    _device_plane(workspace, "workspace", y.device, ws, (torch.uint8,))
+    spans = [(t.data_ptr(), t.data_ptr() + n * t.element_size(), what)
+             for t, n, what in ((y, h * w, "y"), (cb, 64 * nmcu, "cb"), (cr, 64 * nmcu, "cr"), (scan, scan.numel(), "scan"),
+                                (info, 2, "info"), (offsets, intervals + 1, "offsets"), (status, intervals, "status"),
+                                (workspace, ws, "workspace")) if t is not None and n]
+    _disjoint(spans)
+    vp = ctypes.c_void_p
+    args = (vp(scan.data_ptr()), scan.numel(), None if offsets is None else vp(offsets.data_ptr()), vp(y.data_ptr()),
+            None if cb is None else vp(cb.data_ptr()), None if cr is None else vp(cr.data_ptr()), h, w, sub,
+            int(restart_interval), flags, vp(info.data_ptr()), None if status is None else vp(status.data_ptr()),
+            vp(workspace.data_ptr()), workspace.numel(), _stream_ptr(stream))
+    return _bound(load_library().hpdct_decode_scan, args)
+
+
+def decode_info(info) -> dict:
+    """The hpdct_decode_info a bind_decode_scan launch wrote (synchronises)."""
+    raw = info.cpu().numpy().view(np.uint32)
+    return {"bad_intervals": int(raw[0]), "markers_found": int(raw[1]), "marker_errors": int(raw[2])}
+
+
+def decode_scan(scan, *, height, width, components: int = 1, subsampling: str = "420", restart_interval: int = 0,
+                offsets=None, order: str = "zigzag", out=None, stream=None):
+    """The bytes of one baseline Huffman scan -> int16 blocks, on the device: the
+    inverse of encode_scan.  scan: a uint8 device tensor, all of it the scan;
+    height and width: the padded frame; offsets: encode_scan's table, or None
+    and the restart markers are located.  Returns (blocks, info, status): the
+    tuple (y,) or (y, cb, cr) shaped like forward_blocks / forward_rgb_blocks
+    give them (out: such a tuple to fill), {"bad_intervals", "markers_found",
+    "marker_errors"} and the int64 device tensor of one status per interval
+    (code + 256 * failing block; DECODE_STATUS names the codes; 0: clean).
+    Untrusted bytes are safe to pass: a damaged interval is reported, its
+    failing block and the blocks after it are zero.  Synchronises to read info."""
+    torch = _torch()
+    sub = _subsampling(subsampling)
+    _device_plane(scan, "scan", None, 0, (torch.uint8,))
+    h, w, components, side, nmcu, intervals = _decode_geometry(height, width, components, sub, restart_interval)
+    dev = scan.device
+    if out is None:
+        out = (torch.empty((h // 8, w // 8, 64), dtype=torch.int16, device=dev),)
+        if components == 3:
+            out += tuple(torch.empty((h // side, w // side, 64), dtype=torch.int16, device=dev) for _ in range(2))
+    if len(out) != components:
+        raise HpdctError(1, f"out holds {len(out)} block arrays, the scan {components} components")
+    y, cb, cr = (out[0], None, None) if components == 1 else out
+    info = torch.empty(2, dtype=torch.int64, device=dev)
+    status = torch.empty(intervals, dtype=torch.int64, device=dev)
+    ws = decode_workspace_bytes(h, w, components=components, subsampling=subsampling,
+                                restart_interval=restart_interval, scan_bytes=scan.numel())
+    workspace = torch.empty(ws, dtype=torch.uint8, device=dev)
+    bind_decode_scan(scan, offsets, y, cb, cr, info, status, workspace, height=h, width=w, subsampling=subsampling,
+                     restart_interval=restart_interval, order=order, stream=stream)()
+    if stream is not None:
+        stream.synchronize()
+    return tuple(out), decode_info(info), status
+
+
+def jpeg_decode(data, *, device=None):
+    """A baseline JPEG file (bytes) of the kind jpeg_encode writes -> pixels on
+    the device: jpeg_parse on the host, the scan uploaded, decode_scan, then
+    inverse_rgb_frame with the file's tables ((H, W, 3) uint8) or, for a grey
+    file, inverse_blocks ((H, W) uint8, cut from the padded frame).  The grey
+    inverse runs under the library table: a grey file whose table differs from
+    get_quant_table() is refused (set_quant_table first).  A damaged scan
+    (bad_intervals != 0) raises."""
+    torch = _torch()
+    data = bytes(data)
+    lay = jpeg_parse(data)
+    dev = torch.device(device if device is not None else "cuda")
+    h, w, comps, sub = lay["height"], lay["width"], lay["components"], lay["subsampling"]
+    if comps == 1:
+        if not np.array_equal(lay["q_luma"], get_quant_table().reshape(8, 8)):
+            raise HpdctError(2, "the grey file's quant table is not the library table: pass it to set_quant_table() "
+                                "first (inverse_blocks dequantises with the library table)")
+        hp_, wp_ = -(-h // 8) * 8, -(-w // 8) * 8
+    else:
+        hp_, wp_, _, _ = rgb_frame_geometry(h, w, sub)
+    raw = np.frombuffer(data, np.uint8, lay["scan_bytes"], lay["scan_offset"])
+    scan = torch.from_numpy(raw.copy()).to(dev)
+    blocks, info, status = decode_scan(scan, height=hp_, width=wp_, components=comps, subsampling=sub,
+                                       restart_interval=lay["restart_interval"])
+    if info["bad_intervals"]:
+        first = int(torch.nonzero(status)[0])
+        code = int(status[first]) & 255
+        raise HpdctError(1, f"{info['bad_intervals']} damaged restart intervals; the first is interval {first}: "
+                            f"{DECODE_STATUS[code] if code < len(DECODE_STATUS) else code}")
+    if comps == 1:
+        return inverse_blocks(blocks[0], out_dtype=torch.uint8)[:h, :w]
+    return inverse_rgb_frame(*blocks, height=h, width=w, subsampling=sub, q_luma=lay["q_luma"],
+                             q_chroma=lay["q_chroma"])
 
 
 SSE_F32_UNIT = 1.0 / 65536.0  # HPDCT_SSE_F32_UNIT

@@ -495,6 +495,109 @@ hpdct_status hpdct_jpeg_header(uint8_t* h_out, int64_t capacity, int64_t* bytes,
 void hpdct_huffman_table(int kind /* 0 DC-luma, 1 AC-luma, 2 DC-chroma, 3 AC-chroma */, uint8_t* bits16, uint8_t* vals,
                          int* nvals);
 
+/* Baseline-JPEG entropy DEcoding on the device: the inverse of hpdct_encode_scan
+ * (no reference counterpart).  The bytes of one interleaved Huffman scan -> the
+ * int16 block arrays hpdct_inverse_blocks, hpdct_inverse_rgb_blocks and
+ * hpdct_inverse_rgb_frame take.  The geometry (height and width of the padded
+ * frame, d_cb == d_cr == NULL for one component, the MCU order), `flags` (0 or
+ * HPDCT_BLOCKS_NATURAL, permuted on store), the four Annex K.3 tables and the
+ * restart rules are those of hpdct_encode_scan.
+ *   input   d_scan[0 .. bytes), bytes >= 0, any alignment: the scan data alone
+ *           (what hpdct_encode_scan writes; hpdct_jpeg_parse finds it in a
+ *           file).  The bytes are untrusted: whatever they and the offsets
+ *           hold, nothing outside d_scan[0, bytes) is read and nothing outside
+ *           the block arrays, *d_info, d_interval_status and the workspace is
+ *           written; every block of the frame is written exactly once per call.
+ *   where an interval's bytes are
+ *           d_interval_offsets given (the table hpdct_encode_scan writes,
+ *           intervals + 1 uint64, device data and untrusted too): interval i is
+ *           [offs[i], offs[i+1] - 2), the last one [offs[i], offs[i+1]); an
+ *           interval whose bounds are not 0 <= lo <= hi <= bytes has status
+ *           RANGE and reads nothing.
+ *           NULL: the call locates the markers itself.  A marker is any
+ *           position p with scan[p] == 0xFF, 0xD0 <= scan[p+1] <= 0xD7 and
+ *           p + 1 < bytes (stuffing guarantees that no such pair occurs inside
+ *           coded data).  Interval 0 starts at 0, interval i two bytes after the
+ *           i-th marker in byte order, whatever its number; an interval ends at
+ *           the next marker, or at `bytes`.  Intervals with no marker have
+ *           status MISSING; markers beyond intervals - 1 are only counted.  FF
+ *           fill bytes before a marker are not supported: they show as a MARKER
+ *           or TAIL status.
+ *   status  per interval, uint64 = code + 256 * index of the failing block
+ *           within the interval; 0 for a clean interval:
+ *             1 RANGE    bad offsets, as above; block 0
+ *             2 MARKER   an FF inside the interval followed by anything but 00
+ *             3 END      a bit is needed and the interval has no byte left
+ *                        (also an FF as its last byte)
+ *             4 CODE     16 bits read and no code of the component's table matches
+ *             5 INDEX    a (run, size) symbol places a coefficient beyond index
+ *                        63 (judged before its extra bits are read), or a ZRL
+ *                        moves past 64
+ *             6 DC       predictor + difference does not fit int16
+ *             7 TAIL     all blocks decoded, but the rest of the current byte is
+ *                        not all 1 bits, or bytes remain; the blocks stay as
+ *                        decoded, block index 0
+ *             8 MISSING  no marker for this interval; block 0
+ *           MARKER and END are raised when a bit of the byte in question is
+ *           needed, not before.  The predictors are 0 at each interval's start,
+ *           bits are MSB first, extra bits v of size n below 2^(n-1) stand for
+ *           v - 2^n + 1.  For the codes 1-6 and 8 the failing block and every
+ *           later block of that interval are written as 64 zeros; the blocks
+ *           before it keep what was decoded.
+ *   output  *d_info (written by the device) and, when given, d_interval_status
+ *           (`intervals` entries).
+ *   scratch no allocation, no process-wide state: d_workspace, at least
+ *           hpdct_decode_workspace_bytes(...) bytes (8 per interval and 8 per
+ *           4096 bytes of scan; -1 for arguments the call would refuse), is all
+ *           the call uses, so it can be captured into a graph.  Two launches in
+ *           one chain with offsets, four without, asynchronous on `stream`.
+ *   speed   one LANE walks one restart interval, so the call is parallel
+ *           across intervals only.
+ *   Every argument is checked before any device call.
+ *   HPDCT_ERROR_INVALID_VALUE: a null d_scan, d_y, d_info or d_workspace, only
+ *   one of d_cb / d_cr null; sizes that are not positive multiples of the MCU
+ *   or past the tile-count limit; an unknown subsampling (three components);
+ *   restart_interval outside 0..65535; negative bytes; a block, workspace,
+ *   offsets or status pointer that is not 16-byte aligned, d_info not 8-byte
+ *   aligned; workspace_bytes too small; any two buffers overlapping.
+ *   HPDCT_ERROR_UNSUPPORTED: unknown flag bits. */
+typedef struct hpdct_decode_info { /* written by the device; 8-byte aligned */
+    uint32_t bad_intervals;  /* intervals whose status is not 0 */
+    uint32_t markers_found;  /* RSTn markers located (0 when offsets were given) */
+    uint32_t marker_errors;  /* located markers among the first intervals-1 whose number is not i mod 8 */
+    uint32_t reserved;       /* 0 */
+} hpdct_decode_info;
+hpdct_status hpdct_decode_scan(const uint8_t* d_scan, int64_t bytes, const uint64_t* d_interval_offsets /* or NULL */,
+                               int16_t* d_y, int16_t* d_cb, int16_t* d_cr, int64_t height, int64_t width,
+                               hpdct_subsampling sub, int64_t restart_interval, unsigned flags,
+                               hpdct_decode_info* d_info, uint64_t* d_interval_status /* or NULL */,
+                               void* d_workspace, int64_t workspace_bytes, void* stream);
+int64_t hpdct_decode_workspace_bytes(int64_t height, int64_t width, int components, hpdct_subsampling sub,
+                                     int64_t restart_interval, int64_t scan_bytes); /* host; -1 if refused */
+/* The header of a baseline file (host only), the inverse of hpdct_jpeg_header:
+ * walks SOI .. SOS of h_file[0 .. bytes) and never reads outside it.  APPn and
+ * COM segments are skipped; a DQT or DHT segment may hold one table or several.
+ * scan_offset: the first byte after the SOS header; scan_bytes runs to the
+ * first marker after it that is neither FF 00 nor RSTn, which must be EOI.
+ * height, width: the TRUE frame size; q_luma, q_chroma: row-major, as the
+ * library's own tables (q_chroma is not written for one component).
+ * HPDCT_ERROR_UNSUPPORTED, the message naming the reason, for what
+ * hpdct_decode_scan cannot decode: a frame that is not SOF0 with 8-bit samples;
+ * a 16-bit DQT; component counts other than 1 or 3; sampling other than 1x1
+ * (grey), 1x1 / 1x1 / 1x1 or 2x2 / 1x1 / 1x1; Cb and Cr on different quant
+ * tables; a Huffman table selected by a component whose contents differ from
+ * the Annex K luminance table (component 0) or chrominance table (the others);
+ * more than one scan; Ss / Se / Ah / Al other than 0 / 63 / 0 / 0.
+ * HPDCT_ERROR_INVALID_VALUE: a null pointer, a truncated or malformed file. */
+typedef struct hpdct_jpeg_layout {
+    int64_t height, width;
+    int components;
+    hpdct_subsampling sub;
+    int64_t restart_interval, scan_offset, scan_bytes;
+    float q_luma[64], q_chroma[64];
+} hpdct_jpeg_layout;
+hpdct_status hpdct_jpeg_parse(const uint8_t* h_file, int64_t bytes, hpdct_jpeg_layout* out);
+
 /* Work mapping of the kernels (new; the reference has one fixed decomposition
  * per program).  Output is bit-identical in every mapping; only speed differs.
  *   AUTO   per frame: eight lanes per 8x8 tile ("octet") for frames below
