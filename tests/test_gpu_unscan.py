@@ -5,9 +5,9 @@ header's rules, or with the blocks hpdct_encode_scan coded:
 - small frames of every sampling, restart interval, block order, offsets given
   and located; interval counts around a wave's 64 lanes; every row of the policy
   table and a frame beyond the grid cap;
-- the corrupt corpus of test_jpeg_unscan_host.py (which the sanitizer program
-  has walked on the CPU), each scan inside a larger buffer of 0x00 and of 0xFF
-  bytes, the outputs inside sentinel-filled tensors;
+- the corrupt corpus of test_jpeg_unscan_host.py, grey and colour (which the
+  sanitizer program has walked on the CPU), each scan inside a larger buffer of
+  0x00, of 0xFF and of 0xD0 bytes, the outputs inside sentinel-filled tensors;
 - three Pillow-written files; jpeg_decode(jpeg_encode(frame));
 - bound launches on a side stream with reused buffers; a graph capture.
 """
@@ -125,11 +125,14 @@ def test_whole_rows_per_interval_colour(hp, dev):
 # the corrupt corpus
 # ---------------------------------------------------------------------------
 def test_corrupt_corpus(hp, dev):
-    """Every case of the corpus, each scan a slice of one large buffer whose other bytes are 0x00 in one run and
-    0xFF in the other: the results are those of the restatement both times, so a read outside the scan shows as a
-    difference.  The block arrays, status arrays and infos are slices of sentinel-filled tensors; the sentinels
-    between them survive.  All calls of a run are queued, then read back at once."""
+    """Every case of the corpus, grey, 4:2:0 and 4:4:4, each scan a slice of one large buffer whose other bytes are
+    0x00 in one run, 0xFF in another and 0xD0 in a third (a case may name the byte right after its scan): the
+    results are those of the restatement every time, so a read outside the scan shows as a difference -- the
+    marker search reading scan[bytes] makes a marker of a final FF in the 0xD0 run.  The block arrays (y, cb, cr
+    one after the other), status arrays and infos are slices of sentinel-filled tensors; the sentinels between
+    them survive.  All calls of a run are queued, then read back at once."""
     import ctypes
+    import time
     import torch
     cases, results = unscan_corpus.cases_and_expected()
     L = hp.load_library()
@@ -139,50 +142,64 @@ def test_corrupt_corpus(hp, dev):
     for c in cases:
         starts.append(total)
         total += len(c["data"]) + pad + (len(c["data"]) & 1)
-    nblk = max(int(np.prod(c["shapes"][0])) for c in cases)
+    nblk = max(sum(int(np.prod(s)) for s in c["shapes"]) for c in cases)
     nint = max(len(r[1]) for r in results)
-    assert all(c["sampling"] == "grey" for c in cases)
+    assert {c["sampling"] for c in cases} == {"grey", "420", "444"}
     bstride, sstride = 64 * nblk + 64, (nint + 3) // 2 * 2     # a sentinel block and >= 1 sentinel word between
     offs_all = np.zeros((n, (nint + 3) // 2 * 2), np.uint64)      # rows of a 16-byte multiple
     for i, c in enumerate(cases):
         if c["offsets"] is not None:
             offs_all[i, :len(c["offsets"])] = np.asarray(c["offsets"], np.uint64)
     offs_dev = _dev(offs_all.view(np.int64), dev)
-    ws_bytes = max(hp.decode_workspace_bytes(8 * c["shapes"][0][0], 8 * c["shapes"][0][1], restart_interval=c["ri"],
-                                             scan_bytes=len(c["data"])) for c in cases)
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+    ws_bytes = max(hp.decode_workspace_bytes(8 * c["shapes"][0][0], 8 * c["shapes"][0][1], components=len(c["shapes"]),
+                                             subsampling="420" if c["sampling"] == "420" else "444",
+                                             restart_interval=c["ri"], scan_bytes=len(c["data"])) for c in cases)
+    # a call is a chain of small launches that wait for one another: four streams, each with a workspace of its own,
+    # take the cases in turn so that the chains overlap
+    side = [torch.cuda.Stream(device=dev) for _ in range(4)]
+    ws = [torch.empty(ws_bytes, dtype=torch.uint8, device=dev) for _ in side]
     vp = ctypes.c_void_p
-    stream = vp(torch.cuda.current_stream().cuda_stream)
-    for fill in (0x00, 0xff):
+    for fill in (0x00, 0xff, 0xd0):
+        t0 = time.perf_counter()
         host = np.full(total, fill, np.uint8)
         for c, s in zip(cases, starts):
             host[s:s + len(c["data"])] = np.frombuffer(c["data"], np.uint8)
+            if "after" in c:
+                host[s + len(c["data"])] = c["after"]
         buf = _dev(host, dev)
         blocks = torch.full((n, bstride), SENTINEL, dtype=torch.int16, device=dev)
         status = torch.full((n, sstride), -1, dtype=torch.int64, device=dev)
         info = torch.full((n, 2), -1, dtype=torch.int64, device=dev)
         p_buf, p_offs, p_blk, p_info, p_st = (t.data_ptr() for t in (buf, offs_dev, blocks, info, status))
+        torch.cuda.synchronize()                        # the buffers are filled before a side stream reads them
         for i, (c, s) in enumerate(zip(cases, starts)):
             ty, tx = c["shapes"][0]
+            p_y = p_blk + 2 * bstride * i
+            p_cb = p_cr = None
+            if len(c["shapes"]) == 3:                   # cb and cr right behind y: 128-byte multiples
+                ny, nc = 64 * ty * tx, 64 * int(np.prod(c["shapes"][1]))
+                p_cb, p_cr = vp(p_y + 2 * ny), vp(p_y + 2 * (ny + nc))
             st = L.hpdct_decode_scan(vp(p_buf + s), len(c["data"]),
                                      None if c["offsets"] is None else vp(p_offs + 8 * offs_all.shape[1] * i),
-                                     vp(p_blk + 2 * bstride * i), None, None, 8 * ty, 8 * tx, 0, c["ri"], 0,
-                                     vp(p_info + 16 * i), vp(p_st + 8 * sstride * i), vp(ws.data_ptr()), ws_bytes,
-                                     stream)
+                                     vp(p_y), p_cb, p_cr, 8 * ty, 8 * tx, 1 if c["sampling"] == "420" else 0, c["ri"],
+                                     0, vp(p_info + 16 * i), vp(p_st + 8 * sstride * i), vp(ws[i % 4].data_ptr()),
+                                     ws_bytes, vp(side[i % 4].cuda_stream))
             assert st == 0, (c["name"], L.hpdct_last_error_string())
         torch.cuda.synchronize()
         got_b, got_s = blocks.cpu().numpy(), status.cpu().numpy().view(np.uint64)
         got_i = info.cpu().numpy().view(np.uint32).reshape(n, 4)
         wrong = []
         for i, (c, (want, wstatus, found, errors)) in enumerate(zip(cases, results)):
-            k, m = want[0].size, len(wstatus)
-            ok = (np.array_equal(got_b[i, :k], want[0].reshape(-1)) and np.array_equal(got_s[i, :m], wstatus) and
+            flat = np.concatenate([x.reshape(-1) for x in want])
+            k, m = flat.size, len(wstatus)
+            ok = (np.array_equal(got_b[i, :k], flat) and np.array_equal(got_s[i, :m], wstatus) and
                   got_i[i].tolist() == [int((wstatus != 0).sum()), found, errors, 0])
             ok = ok and bool((got_b[i, k:] == SENTINEL).all()) and bool((got_s[i, m:] == np.uint64(2 ** 64 - 1)).all())
             if not ok:
                 wrong.append(c["name"])
         assert not wrong, (hex(fill), len(wrong), wrong[:10])
         assert np.array_equal(buf.cpu().numpy(), host)
+        print("corpus, surroundings %#04x: %d cases in %.2f s" % (fill, n, time.perf_counter() - t0))
 
 
 # ---------------------------------------------------------------------------

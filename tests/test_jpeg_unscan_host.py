@@ -366,8 +366,12 @@ def test_unscan_clean_under_asan_ubsan(tmp_path):
     """A stand-alone program (tests/tools/asan_unscan_check.cpp, its own main) with hpdct_api.cpp compiled by g++
     under tests/tools/asan.mk's ASan + UBSan flags: hpdct_decode_scan's refusals, hpdct_jpeg_parse on every
     truncation and corruption of a file, and unscan::walk_interval -- the function the decode kernel wraps -- over
-    the whole corpus, compared with the restatement's results (the file written here, next to the program).  CPU
-    only: nothing is launched, nothing is loaded into Python."""
+    the whole corpus (grey and colour) and the built scans of tests/unscan_built.py, each at the eight addresses
+    mod 8, compared with the restatement's results (the file written here, next to the program).  CPU only:
+    nothing is launched, nothing is loaded into Python."""
+    import unscan_built
     cases, results = unscan_corpus.cases_and_expected()
-    unscan_corpus.write_file(str(tmp_path / "unscan_corpus.bin"), cases, results)
+    built = unscan_built.corpus_cases()
+    unscan_corpus.write_file(str(tmp_path / "unscan_corpus.bin"), list(cases) + built,
+                             list(results) + [unscan_corpus.expected(c) for c in built])
     host_programs.sanitised_check("asan_unscan_check", tmp_path, "hpdct_unscan.o")

@@ -8,7 +8,9 @@
 //   3. unscan::walk_interval, the very function the decode kernel wraps, over the
 //      corrupt corpus tests/unscan_corpus.py wrote next to this program
 //      (unscan_corpus.bin), scans, offset tables and block arrays in heap buffers
-//      of exactly their size, compared with what tests/jpeg_unscan.py expects.
+//      of exactly their size, compared with what tests/jpeg_unscan.py expects;
+//      every scan at each of the eight addresses mod 8 (the walk's byte cache
+//      loads aligned words, so what it loads depends on where the scan lies).
 // Built and run by tests/test_jpeg_unscan_host.py.
 #include <cstdint>
 #include <cstdio>
@@ -205,9 +207,10 @@ struct File {
     }
 };
 
-// one case of the corpus through the walker, as the kernels go through it: the markers located by a plain loop
+// one case of the corpus through the walker, as the kernels go through it: the markers located by a plain loop.
+// shift: the scan's address mod 8; it ends where its heap buffer ends, the bytes before it are FF.
 template <bool kNatural>
-bool run_case(File& f, uint32_t index) {
+bool run_case(File& f, uint32_t index, uint32_t shift) {
     using namespace hpdct;
     const uint32_t comps = f.u32(), sub = f.u32(), ty = f.u32(), tx = f.u32(), ri = f.u32(), has_offs = f.u32(),
                    intervals = f.u32(), want_found = f.u32(), want_errors = f.u32();
@@ -224,8 +227,11 @@ bool run_case(File& f, uint32_t index) {
     g.bpm = comps == 1u ? 1u : s420 ? 6u : 3u;
     if (g.intervals != intervals) return false;
     // exact-size heap buffers (at least one element: a zero-size new[] may not be read at all, which is the point)
-    std::unique_ptr<uint8_t[]> scan_buf(new uint8_t[bytes]);
-    f.read(scan_buf.get(), bytes);
+    std::unique_ptr<uint8_t[]> scan_heap(new uint8_t[shift + bytes]);  // operator new[]: 16-byte aligned
+    if ((reinterpret_cast<uintptr_t>(scan_heap.get()) & 7u) != 0u) return false;
+    std::memset(scan_heap.get(), 0xff, shift);
+    uint8_t* const scan_buf = scan_heap.get() + shift;
+    f.read(scan_buf, bytes);
     std::unique_ptr<uint64_t[]> offs(new uint64_t[has_offs ? intervals + 1u : 0u]);
     if (has_offs) f.read(offs.get(), 8u * (intervals + 1u));
     std::vector<uint64_t> want_status(intervals);
@@ -242,7 +248,7 @@ bool run_case(File& f, uint32_t index) {
     uint64_t found = 0, errors = 0;
     if (!has_offs)
         for (uint64_t p = 0; p < bytes; ++p)
-            if (unscan::marker_at(scan_buf.get(), p, bytes)) {
+            if (unscan::marker_at(scan_buf, p, bytes)) {
                 if (found < intervals) {
                     mpos[found] = p;
                     if (found + 1u < intervals && (scan_buf[p + 1u] & 7u) != (found & 7u)) ++errors;
@@ -258,7 +264,7 @@ bool run_case(File& f, uint32_t index) {
         const uint32_t pre = has_offs ? unscan::bounds_given(offs.get(), iv, intervals, bytes, lo, hi)
                                       : unscan::bounds_located(mpos.get(), found, iv, bytes, lo, hi);
         alignas(16) uint32_t row[32];
-        const uint64_t st = unscan::walk_interval<kNatural>(scan_buf.get(), lo, hi, pre, iv, g, &tables, order, row,
+        const uint64_t st = unscan::walk_interval<kNatural>(scan_buf, lo, hi, pre, iv, g, &tables, order, row,
                                                             y.get(), nc ? cb.get() : nullptr, nc ? cr.get() : nullptr);
         same = same && st == want_status[iv];
     }
@@ -272,7 +278,9 @@ bool run_case(File& f, uint32_t index) {
     same = same && blocks_equal(y.get(), want_y) && blocks_equal(cb.get(), want_cb) && blocks_equal(cr.get(), want_cr);
     if (!same) {
         ++g_bad;
-        if (g_bad < 20) std::printf("MISMATCH corpus case %u (%s order)\n", index, kNatural ? "natural" : "zig-zag");
+        if (g_bad < 20)
+            std::printf("MISMATCH corpus case %u (%s order, address %u mod 8)\n", index,
+                        kNatural ? "natural" : "zig-zag", shift);
     }
     return true;
 }
@@ -294,16 +302,24 @@ void corpus(const char* argv0) {
     const uint32_t count = f.u32();
     uint32_t done = 0;
     for (; done < count; ++done) {
+        // zig-zag order at every address mod 8, natural order (the same walk, another store index) at two
         const size_t at = f.p;
-        if (!run_case<false>(f, done)) break;
-        f.p = at;
-        if (!run_case<true>(f, done)) break;
+        bool read = true;
+        for (uint32_t shift = 0; shift < 8u && read; ++shift) {
+            f.p = at;
+            read = run_case<false>(f, done, shift);
+            if (read && (shift == 0u || shift == 5u)) {
+                f.p = at;
+                read = run_case<true>(f, done, shift);
+            }
+        }
+        if (!read) break;
     }
     if (done != count || f.p != f.d.size() || count < 1000u) {
         ++g_bad;
         std::printf("MISMATCH corpus file: %u of %u cases read\n", done, count);
     }
-    std::printf("asan_unscan_check: %u corpus cases, both block orders\n", done);
+    std::printf("asan_unscan_check: %u corpus cases, eight addresses, both block orders\n", done);
 }
 }  // namespace
 
