@@ -91,6 +91,16 @@ enum : unsigned {
 constexpr uint32_t unscan_lanes_of(unsigned var) {
     return (var & kUnscanLanes16) ? 16u : (var & kUnscanLanes4) ? 4u : (var & kUnscanLanes1) ? 1u : 64u;
 }
+// the split entropy decoder's kernels (hpdct_unscan_split.hpp): which one, in bits 29..31; its serial kernel also
+// reads the kUnscanLanes* bits, its write and serial kernels kScanNatural
+enum : unsigned {
+    kUnsplitPlan = 1u << 29,
+    kUnsplitSettle = 2u << 29,
+    kUnsplitOffsets = 3u << 29,
+    kUnsplitClear = 4u << 29,
+    kUnsplitWrite = 5u << 29,
+    kUnsplitSerial = 6u << 29,
+};
 // Bits only the product kernels give a meaning to: the tools' A/B variant
 // bits must stay clear of them (static_assert in tools/kbench_variants.hpp).
 constexpr unsigned kProductOnlyVarBits = kVarFastDivChecked | kVarJpegQ;

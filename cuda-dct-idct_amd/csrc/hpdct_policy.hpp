@@ -17,7 +17,8 @@ namespace policy {
 // kRgb: fdct_rgb_kernel / idct_rgb_kernel (hpdct_rgb.hpp)
 // kScan: scan_code_kernel / scan_offsets_kernel (hpdct_scan.hpp)
 // kUnscan: unscan_locate_kernel / unscan_rank_kernel / unscan_decode_kernel (hpdct_unscan.hpp)
-enum class Family { kTile, kOctet, kDuo, kDuoFwdU8, kRowFirstDuo, kRtDuo, kRtTile, kBlocks, kRgb, kScan, kUnscan };
+// kUnsplit: the unsplit_*_kernel of hpdct_unscan_split.hip
+enum class Family { kTile, kOctet, kDuo, kDuoFwdU8, kRowFirstDuo, kRtDuo, kRtTile, kBlocks, kRgb, kScan, kUnscan, kUnsplit };
 enum class Elem { kU8, kI8, kF32 };
 
 // var: the kernel's kVar; kDuoFwdU8 and kRt* carry their quotient and straddle bits there
@@ -409,6 +410,61 @@ inline Choice unscan_locate(uint64_t chunks, bool place) {
             wgs < kUnscanMaxWgs ? static_cast<uint32_t>(wgs) : kUnscanMaxWgs, 1u};
 }
 inline Choice unscan_rank() { return {Family::kUnscan, with_block<1024>(kUnscanRank), 1024u, 0u, 1u, 1u}; }
+
+// The split entropy decoder (hpdct_unscan_split.hpp): a lane walks a SEGMENT of
+// kUnsplitSegBytes bytes, a workgroup of kUnsplitGroup lanes a group of as many
+// consecutive segments of one interval, and kUnsplitRounds launches after the
+// first carry a changed exit from one group to the next.  A segment must hold
+// several block ends for the walks to fall into step (a block of noise at the
+// default table is some 50 bytes), and a CPU simulation needed 1-4 rounds of
+// neighbour exchange at 256 bytes for all but scans without a single EOB; those
+// rounds run inside a group, in LDS, so a launch between groups is needed only
+// where a wrong exit crosses a group's end.  The settle and write kernels keep
+// the tables and a state per lane in LDS (10.5 KiB a workgroup), no block row.
+// An interval of at most (kUnsplitRounds + 1) groups, 320 KiB, always settles;
+// a longer one that does not is walked by one lane, as every interval shorter
+// than kUnsplitMinBytes is.  The threshold, measured at 8192^2 with every
+// interval split against hpdct_decode_scan on the same scans, offsets given, us
+// (tools/unscan_split_probe.py, profiles/r12/unscan_split_probe.log and
+// unscan_split_threshold.log; the two passes differ by under 1 %):
+//   bytes an interval (intervals)      serial     split
+//        220  (131,072) grey noise        578    34,868
+//        875   (32,768) grey noise      1,584    20,963
+//      1,749   (16,384) grey noise      2,869    12,607
+//      2,172      (512) 4:2:0 smooth    4,088     2,985
+//      3,496    (8,192) grey noise      8,053     7,247
+//      6,718    (4,096) 4:2:0 noise     8,885     7,238
+//      6,990    (4,096) grey noise      9,250     4,948
+//     13,978    (2,048) grey noise     16,571     3,861
+//     27,954    (1,024) grey noise     35,671     2,963    (one MCU row)
+//     53,734      (512) 4:2:0 noise    57,979     4,696    (one MCU row)
+//    891,110        (1) 1080p noise   780,994     2,600    (no restart markers)
+// A group holds one interval's segments only, so thousands of short intervals
+// run workgroups of a few lanes each, and the chain costs 2 ms at 8192^2 whatever
+// it decodes (the clear of 128 MiB of blocks, eleven launches).  3,496 bytes is
+// the shortest interval at which the split call won with thousands of intervals;
+// the threshold is the 13 segments below it.  (At 2,172 bytes it won with 512.)
+constexpr uint32_t kUnsplitSegBytes = 256, kUnsplitGroup = 256, kUnsplitRounds = 4;
+constexpr uint64_t kUnsplitMinBytes = 3328;
+constexpr uint32_t kUnsplitMaxWgs = 1u << 16;  // beyond: a workgroup takes every kUnsplitMaxWgs-th group
+inline Choice unsplit_plan() { return {Family::kUnsplit, with_block<1024>(kUnsplitPlan), 1024u, 0u, 1u, 1u}; }
+// groups: the budget of groups (every one may be in use)
+inline Choice unsplit_groups(uint64_t groups, unsigned kind, bool natural) {
+    return {Family::kUnsplit, with_block<256>(kind | (natural ? kScanNatural : 0u)), 256u, 0u,
+            groups < kUnsplitMaxWgs ? static_cast<uint32_t>(groups < 1u ? 1u : groups) : kUnsplitMaxWgs, 1u};
+}
+inline Choice unsplit_settle(uint64_t groups) { return unsplit_groups(groups, kUnsplitSettle, false); }
+inline Choice unsplit_write(uint64_t groups, bool natural) { return unsplit_groups(groups, kUnsplitWrite, natural); }
+// one workgroup per interval
+inline Choice unsplit_offsets(uint32_t intervals) { return unsplit_groups(intervals, kUnsplitOffsets, false); }
+// units: 16-byte pieces of all the frame's blocks, one per lane
+inline Choice unsplit_clear(uint64_t units) { return unsplit_groups((units + 255u) / 256u, kUnsplitClear, false); }
+// the serial pass: the parent's decode launch for this interval count
+inline Choice unsplit_serial(const UnscanCall& c) {
+    Choice ch = unscan_decode(c);
+    ch.family = Family::kUnsplit, ch.var |= kUnsplitSerial;
+    return ch;
+}
 
 // launch_roundtrip.  The two-lanes-per-tile round trip (hpdct_rt_duo.hpp) for
 // the verified quotient (qmode 1 or 2) with any reconstruction, when its sums

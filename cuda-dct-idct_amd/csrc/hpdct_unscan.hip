@@ -17,9 +17,8 @@ hipError_t launch_unscan_decode(const policy::Choice& c, hipStream_t s, const ui
 }
 }  // namespace
 
-hipError_t launch_unscan(const uint8_t* scan, uint64_t bytes, const uint64_t* offs, int16_t* y, int16_t* cb,
-                         int16_t* cr, const scan::ScanGrid& g, bool natural, hpdct_decode_info* info, uint64_t* status,
-                         void* workspace, hipStream_t s) {
+hipError_t launch_unscan_locate(const uint8_t* scan, uint64_t bytes, const uint64_t* offs, const scan::ScanGrid& g,
+                                hpdct_decode_info* info, void* workspace, hipStream_t s) {
     // the workspace: a uint64 per interval (a marker's position), then a uint64 per chunk (its count, then its rank)
     uint64_t* mpos = static_cast<uint64_t*>(workspace);
     uint64_t* counts = mpos + unscan::marker_words(g.intervals);
@@ -36,6 +35,14 @@ hipError_t launch_unscan(const uint8_t* scan, uint64_t bytes, const uint64_t* of
         if (hipError_t e = launch_choice<kPlaceV, unscan_locate_kernel<kPlaceV>>(
                 policy::unscan_locate(nchunks, true), s, scan, bytes, nchunks, counts, mpos, g.intervals, info))
             return e;
+    return hipSuccess;
+}
+
+hipError_t launch_unscan(const uint8_t* scan, uint64_t bytes, const uint64_t* offs, int16_t* y, int16_t* cb,
+                         int16_t* cr, const scan::ScanGrid& g, bool natural, hpdct_decode_info* info, uint64_t* status,
+                         void* workspace, hipStream_t s) {
+    if (hipError_t e = launch_unscan_locate(scan, bytes, offs, g, info, workspace, s)) return e;
+    const uint64_t* mpos = static_cast<const uint64_t*>(workspace);
     policy::UnscanCall pc;
     pc.intervals = g.intervals, pc.natural = natural;
     const policy::Choice c = policy::unscan_decode(pc);

@@ -338,6 +338,9 @@ HPDCT_HD uint64_t walk_interval(const uint8_t* scan, uint64_t lo, uint64_t hi, u
 hipError_t launch_unscan(const uint8_t* scan, uint64_t bytes, const uint64_t* offs, int16_t* y, int16_t* cb,
                          int16_t* cr, const scan::ScanGrid& g, bool natural, hpdct_decode_info* info, uint64_t* status,
                          void* workspace, hipStream_t s);
+// the marker search's launches alone (count, rank, place; the rank launch alone with offsets), for hpdct_unscan_split.hpp
+hipError_t launch_unscan_locate(const uint8_t* scan, uint64_t bytes, const uint64_t* offs, const scan::ScanGrid& g,
+                                hpdct_decode_info* info, void* workspace, hipStream_t s);
 
 }  // namespace hpdct
 

@@ -61,6 +61,7 @@ C_SYMBOLS = [
     "hpdct_encode_scan", "hpdct_scan_bound", "hpdct_scan_workspace_bytes", "hpdct_jpeg_header",
     "hpdct_huffman_table",
     "hpdct_decode_scan", "hpdct_decode_workspace_bytes", "hpdct_jpeg_parse",
+    "hpdct_decode_scan_split", "hpdct_decode_split_workspace_bytes", "hpdct_decode_split_geometry",
 ]
 MAPPINGS = {"auto": 0, "tile": 1, "octet": 2, "duo": 3}
 BASELINES = {"reference_3pass": 0, "fastappr_3pass": 1}
@@ -152,6 +153,13 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.hpdct_decode_scan.restype = ctypes.c_int
     lib.hpdct_decode_workspace_bytes.argtypes = [i64, i64, ctypes.c_int, ctypes.c_int, i64, i64]
     lib.hpdct_decode_workspace_bytes.restype = i64
+    lib.hpdct_decode_scan_split.argtypes = [vp, i64, vp, vp, vp, vp, i64, i64, ctypes.c_int, i64, ctypes.c_uint, i64,
+                                            vp, vp, vp, i64, vp]
+    lib.hpdct_decode_scan_split.restype = ctypes.c_int
+    lib.hpdct_decode_split_workspace_bytes.argtypes = [i64, i64, ctypes.c_int, ctypes.c_int, i64, i64]
+    lib.hpdct_decode_split_workspace_bytes.restype = i64
+    lib.hpdct_decode_split_geometry.argtypes = [ctypes.POINTER(ctypes.c_int)] * 3
+    lib.hpdct_decode_split_geometry.restype = None
     lib.hpdct_jpeg_parse.argtypes = [vp, i64, vp]
     lib.hpdct_jpeg_parse.restype = ctypes.c_int
     lib.hpdct_status_string.restype = ctypes.c_char_p
@@ -988,6 +996,50 @@ def decode_workspace_bytes(height, width, *, components=1, subsampling="420", re
     return n
 
 
+def _bind_decode(split_min_bytes, scan, offsets, y, cb, cr, info, status, workspace, height, width, subsampling,
+                 restart_interval, order, stream):
+    """bind_decode_scan (split_min_bytes None) and bind_decode_scan_split: the same buffers and checks, the info
+    and the workspace the call's own."""
+    torch = _torch()
+    split = split_min_bytes is not None
+    sub, flags = _subsampling(subsampling), _block_flags(order)
+    _device_plane(y, "y blocks", None, 0, (torch.int16,))
+    if (cb is None) != (cr is None):
+        raise HpdctError(1, "cb and cr are both given or both None")
+    h, w = _blocks_hw(y, height, width, "y blocks")
+    h, w, components, side, nmcu, intervals = _decode_geometry(h, w, 1 if cb is None else 3, sub, restart_interval)
+    if split and int(split_min_bytes) < 0:
+        raise HpdctError(1, f"split_min_bytes must not be negative (got {split_min_bytes})")
+    _device_plane(scan, "scan", y.device, 0, (torch.uint8,))
+    _device_plane(y, "y blocks", None, h * w, (torch.int16,))
+    if components == 3:
+        for t, what in ((cb, "cb blocks"), (cr, "cr blocks")):
+            _device_plane(t, what, y.device, 64 * nmcu, (torch.int16,))
+    ninfo = 4 if split else 2
+    _device_plane(info, "info", y.device, ninfo, (torch.int64,))
+    if offsets is not None:
+        _device_plane(offsets, "offsets", y.device, intervals + 1, (torch.int64,))
+    if status is not None:
+        _device_plane(status, "status", y.device, intervals, (torch.int64,))
+    ws = (decode_split_workspace_bytes if split else decode_workspace_bytes)(
+        h, w, components=components, subsampling=subsampling, restart_interval=restart_interval,
+        scan_bytes=scan.numel())
+    _device_plane(workspace, "workspace", y.device, ws, (torch.uint8,))
+    spans = [(t.data_ptr(), t.data_ptr() + n * t.element_size(), what)
+             for t, n, what in ((y, h * w, "y"), (cb, 64 * nmcu, "cb"), (cr, 64 * nmcu, "cr"), (scan, scan.numel(), "scan"),
+                                (info, ninfo, "info"), (offsets, intervals + 1, "offsets"), (status, intervals, "status"),
+                                (workspace, ws, "workspace")) if t is not None and n]
+    _disjoint(spans)
+    vp = ctypes.c_void_p
+    args = (vp(scan.data_ptr()), scan.numel(), None if offsets is None else vp(offsets.data_ptr()), vp(y.data_ptr()),
+            None if cb is None else vp(cb.data_ptr()), None if cr is None else vp(cr.data_ptr()), h, w, sub,
+            int(restart_interval), flags) + ((int(split_min_bytes),) if split else ()) + (
+            vp(info.data_ptr()), None if status is None else vp(status.data_ptr()),
+            vp(workspace.data_ptr()), workspace.numel(), _stream_ptr(stream))
+    lib = load_library()
+    return _bound(lib.hpdct_decode_scan_split if split else lib.hpdct_decode_scan, args)
+
+
 def bind_decode_scan(scan, offsets, y, cb, cr, info, status, workspace, *, height=None, width=None,
                      subsampling: str = "420", restart_interval: int = 0, order: str = "zigzag", stream=None):
     """Pre-resolved hpdct_decode_scan launch on the given buffers: a
@@ -997,37 +1049,48 @@ def bind_decode_scan(scan, offsets, y, cb, cr, info, status, workspace, *, heigh
     or intervals + 1 int64; y, cb, cr: int16 block arrays to fill (cb = cr = None:
     grey); info: 16 bytes (two int64); status: None or `intervals` int64;
     workspace: uint8."""
-    torch = _torch()
-    sub, flags = _subsampling(subsampling), _block_flags(order)
-    _device_plane(y, "y blocks", None, 0, (torch.int16,))
-    if (cb is None) != (cr is None):
-        raise HpdctError(1, "cb and cr are both given or both None")
-    h, w = _blocks_hw(y, height, width, "y blocks")
-    h, w, components, side, nmcu, intervals = _decode_geometry(h, w, 1 if cb is None else 3, sub, restart_interval)
-    _device_plane(scan, "scan", y.device, 0, (torch.uint8,))
-    _device_plane(y, "y blocks", None, h * w, (torch.int16,))
-    if components == 3:
-        for t, what in ((cb, "cb blocks"), (cr, "cr blocks")):
-            _device_plane(t, what, y.device, 64 * nmcu, (torch.int16,))
-    _device_plane(info, "info", y.device, 2, (torch.int64,))
-    if offsets is not None:
-        _device_plane(offsets, "offsets", y.device, intervals + 1, (torch.int64,))
-    if status is not None:
-        _device_plane(status, "status", y.device, intervals, (torch.int64,))
-    ws = decode_workspace_bytes(h, w, components=components, subsampling=subsampling,
-                                restart_interval=restart_interval, scan_bytes=scan.numel())
-    _device_plane(workspace, "workspace", y.device, ws, (torch.uint8,))
-    spans = [(t.data_ptr(), t.data_ptr() + n * t.element_size(), what)
-             for t, n, what in ((y, h * w, "y"), (cb, 64 * nmcu, "cb"), (cr, 64 * nmcu, "cr"), (scan, scan.numel(), "scan"),
-                                (info, 2, "info"), (offsets, intervals + 1, "offsets"), (status, intervals, "status"),
-                                (workspace, ws, "workspace")) if t is not None and n]
-    _disjoint(spans)
-    vp = ctypes.c_void_p
-    args = (vp(scan.data_ptr()), scan.numel(), None if offsets is None else vp(offsets.data_ptr()), vp(y.data_ptr()),
-            None if cb is None else vp(cb.data_ptr()), None if cr is None else vp(cr.data_ptr()), h, w, sub,
-            int(restart_interval), flags, vp(info.data_ptr()), None if status is None else vp(status.data_ptr()),
-            vp(workspace.data_ptr()), workspace.numel(), _stream_ptr(stream))
-    return _bound(load_library().hpdct_decode_scan, args)
+    return _bind_decode(None, scan, offsets, y, cb, cr, info, status, workspace, height, width, subsampling,
+                        restart_interval, order, stream)
+
+
+def decode_split_geometry():
+    """hpdct_decode_split_geometry: (bytes of a segment, segments of a group, launches between groups)."""
+    v = [ctypes.c_int(0) for _ in range(3)]
+    load_library().hpdct_decode_split_geometry(*(ctypes.byref(x) for x in v))
+    return tuple(int(x.value) for x in v)
+
+
+def decode_split_workspace_bytes(height, width, *, components=1, subsampling="420", restart_interval=0,
+                                 scan_bytes=0) -> int:
+    """hpdct_decode_split_workspace_bytes: decode_workspace_bytes and 16 bytes per interval and group, 64 per
+    segment more."""
+    n = int(load_library().hpdct_decode_split_workspace_bytes(int(height), int(width), int(components),
+                                                              _subsampling(subsampling), int(restart_interval),
+                                                              int(scan_bytes)))
+    if n < 0:
+        _check(1)
+    return n
+
+
+def bind_decode_scan_split(scan, offsets, y, cb, cr, info, status, workspace, *, height=None, width=None,
+                           subsampling: str = "420", restart_interval: int = 0, order: str = "zigzag",
+                           split_min_bytes: int = 0, stream=None):
+    """Pre-resolved hpdct_decode_scan_split launch: bind_decode_scan's buffers,
+    but info of 32 bytes (four int64) and a workspace of
+    decode_split_workspace_bytes(...) bytes.  split_min_bytes: intervals of at
+    least this many bytes are split (0: the library's choice; 1: all but empty
+    ones).  Eleven launches with offsets, thirteen without, none of which waits
+    for the host: it can be captured into a graph."""
+    return _bind_decode(int(split_min_bytes), scan, offsets, y, cb, cr, info, status, workspace, height, width,
+                        subsampling, restart_interval, order, stream)
+
+
+def decode_split_info(info) -> dict:
+    """The hpdct_decode_split_info a bind_decode_scan_split launch wrote (synchronises)."""
+    raw = info.cpu().numpy().view(np.uint32)
+    return {"bad_intervals": int(raw[0]), "markers_found": int(raw[1]), "marker_errors": int(raw[2]),
+            "split_intervals": int(raw[4]), "serial_intervals": int(raw[5]), "unsettled_intervals": int(raw[6]),
+            "rounds": int(raw[7])}
 
 
 def decode_info(info) -> dict:
@@ -1037,7 +1100,8 @@ def decode_info(info) -> dict:
 
 
 def decode_scan(scan, *, height, width, components: int = 1, subsampling: str = "420", restart_interval: int = 0,
-                offsets=None, order: str = "zigzag", out=None, stream=None):
+                offsets=None, order: str = "zigzag", out=None, stream=None, method: str = "serial",
+                split_min_bytes: int = 0):
     """The bytes of one baseline Huffman scan -> int16 blocks, on the device: the
     inverse of encode_scan.  scan: a uint8 device tensor, all of it the scan;
     height and width: the padded frame; offsets: encode_scan's table, or None
@@ -1047,9 +1111,16 @@ def decode_scan(scan, *, height, width, components: int = 1, subsampling: str = 
     "marker_errors"} and the int64 device tensor of one status per interval
     (code + 256 * failing block; DECODE_STATUS names the codes; 0: clean).
     Untrusted bytes are safe to pass: a damaged interval is reported, its
-    failing block and the blocks after it are zero.  Synchronises to read info."""
+    failing block and the blocks after it are zero.  method: "serial"
+    (hpdct_decode_scan, one lane per restart interval) or "split"
+    (hpdct_decode_scan_split, parallel inside an interval of at least
+    split_min_bytes bytes as well: the same blocks and status, and info has the
+    four counters of decode_split_info besides).  Synchronises to read info."""
     torch = _torch()
     sub = _subsampling(subsampling)
+    if method not in ("serial", "split"):
+        raise ValueError(f"method must be 'serial' or 'split' (got {method!r})")
+    split = method == "split"
     _device_plane(scan, "scan", None, 0, (torch.uint8,))
     h, w, components, side, nmcu, intervals = _decode_geometry(height, width, components, sub, restart_interval)
     dev = scan.device
@@ -1060,28 +1131,37 @@ def decode_scan(scan, *, height, width, components: int = 1, subsampling: str = 
     if len(out) != components:
         raise HpdctError(1, f"out holds {len(out)} block arrays, the scan {components} components")
     y, cb, cr = (out[0], None, None) if components == 1 else out
-    info = torch.empty(2, dtype=torch.int64, device=dev)
+    info = torch.empty(4 if split else 2, dtype=torch.int64, device=dev)
     status = torch.empty(intervals, dtype=torch.int64, device=dev)
-    ws = decode_workspace_bytes(h, w, components=components, subsampling=subsampling,
-                                restart_interval=restart_interval, scan_bytes=scan.numel())
+    ws = (decode_split_workspace_bytes if split else decode_workspace_bytes)(
+        h, w, components=components, subsampling=subsampling, restart_interval=restart_interval,
+        scan_bytes=scan.numel())
     workspace = torch.empty(ws, dtype=torch.uint8, device=dev)
-    bind_decode_scan(scan, offsets, y, cb, cr, info, status, workspace, height=h, width=w, subsampling=subsampling,
-                     restart_interval=restart_interval, order=order, stream=stream)()
+    _bind_decode(int(split_min_bytes) if split else None, scan, offsets, y, cb, cr, info, status, workspace, h, w,
+                 subsampling, restart_interval, order, stream)()
     if stream is not None:
         stream.synchronize()
-    return tuple(out), decode_info(info), status
+    return tuple(out), (decode_split_info if split else decode_info)(info), status
 
 
-def jpeg_decode(data, *, device=None):
+SPLIT_MIN_BYTES = 3328  # hpdct_policy.hpp's kUnsplitMinBytes: what split_min_bytes = 0 and method="auto" mean
+
+
+def jpeg_decode(data, *, device=None, method: str = "auto"):
     """A baseline JPEG file (bytes) of the kind jpeg_encode writes -> pixels on
     the device: jpeg_parse on the host, the scan uploaded, decode_scan, then
     inverse_rgb_frame with the file's tables ((H, W, 3) uint8) or, for a grey
     file, inverse_blocks ((H, W) uint8, cut from the padded frame).  The grey
     inverse runs under the library table: a grey file whose table differs from
     get_quant_table() is refused (set_quant_table first).  A damaged scan
-    (bad_intervals != 0) raises."""
+    (bad_intervals != 0) raises.  method: "serial" or "split" as decode_scan
+    takes them, or "auto": the split call when the scan has SPLIT_MIN_BYTES
+    bytes per restart interval or more (a file without restart markers is one
+    interval), the serial call below that."""
     torch = _torch()
     data = bytes(data)
+    if method not in ("auto", "serial", "split"):
+        raise ValueError(f"method must be 'auto', 'serial' or 'split' (got {method!r})")
     lay = jpeg_parse(data)
     dev = torch.device(device if device is not None else "cuda")
     h, w, comps, sub = lay["height"], lay["width"], lay["components"], lay["subsampling"]
@@ -1094,8 +1174,11 @@ def jpeg_decode(data, *, device=None):
         hp_, wp_, _, _ = rgb_frame_geometry(h, w, sub)
     raw = np.frombuffer(data, np.uint8, lay["scan_bytes"], lay["scan_offset"])
     scan = torch.from_numpy(raw.copy()).to(dev)
+    if method == "auto":
+        intervals = _decode_geometry(hp_, wp_, comps, _subsampling(sub), lay["restart_interval"])[5]
+        method = "split" if lay["scan_bytes"] >= SPLIT_MIN_BYTES * intervals else "serial"
     blocks, info, status = decode_scan(scan, height=hp_, width=wp_, components=comps, subsampling=sub,
-                                       restart_interval=lay["restart_interval"])
+                                       restart_interval=lay["restart_interval"], method=method)
     if info["bad_intervals"]:
         first = int(torch.nonzero(status)[0])
         code = int(status[first]) & 255

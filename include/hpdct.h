@@ -552,7 +552,10 @@ void hpdct_huffman_table(int kind /* 0 DC-luma, 1 AC-luma, 2 DC-chroma, 3 AC-chr
  *           the call uses, so it can be captured into a graph.  Two launches in
  *           one chain with offsets, four without, asynchronous on `stream`.
  *   speed   one LANE walks one restart interval, so the call is parallel
- *           across intervals only.
+ *           across intervals only; hpdct_decode_scan_split
+ *           below is parallel inside an interval as well: 12 times faster at
+ *           one MCU row of noise per interval at 8192^2, slower below some
+ *           3 KB an interval.
  *   Every argument is checked before any device call.
  *   HPDCT_ERROR_INVALID_VALUE: a null d_scan, d_y, d_info or d_workspace, only
  *   one of d_cb / d_cr null; sizes that are not positive multiples of the MCU
@@ -574,6 +577,62 @@ hpdct_status hpdct_decode_scan(const uint8_t* d_scan, int64_t bytes, const uint6
                                void* d_workspace, int64_t workspace_bytes, void* stream);
 int64_t hpdct_decode_workspace_bytes(int64_t height, int64_t width, int components, hpdct_subsampling sub,
                                      int64_t restart_interval, int64_t scan_bytes); /* host; -1 if refused */
+/* hpdct_decode_scan, parallel INSIDE a restart interval as well (DESIGN.md
+ * 4.10): the arguments of hpdct_decode_scan and split_min_bytes.  An interval of
+ * at least split_min_bytes bytes is split into segments, one lane each; 0: the
+ * library's choice (3328); 1: every interval that is not empty; negative:
+ * HPDCT_ERROR_INVALID_VALUE.
+ *   contract  the block arrays, the status array and the first 16 bytes of
+ *           *d_info are, for every input whatever, bit for bit what
+ *           hpdct_decode_scan writes.  Everything its paragraph says about
+ *           untrusted bytes and offsets holds unchanged, except that a block
+ *           may be stored more than once.
+ *   method  a lane walks a 256-byte segment from its first byte as if a block
+ *           began there; Huffman codes fall into step, so most walks end where
+ *           the true decode stands there.  Each lane then walks again from its
+ *           predecessor's exit until nothing changes: inside a group of 256
+ *           segments in one launch, between groups in 4 launches more.  The
+ *           blocks of an interval are taken from the split walks only when every
+ *           segment entered at its predecessor's exit (segment 0 at the true
+ *           start), no walk met an error, the blocks number what the geometry
+ *           says, the interval ends as TAIL demands and every DC fits int16.
+ *           Every other interval is decoded as hpdct_decode_scan decodes it, by
+ *           one lane, which also gives the exact status.  An interval of at most
+ *           5 groups (320 KiB) always reaches the fixed point.
+ *   info    hpdct_decode_split_info, 8-byte aligned: hpdct_decode_info's four
+ *           words, then the intervals that were split, those walked by one lane
+ *           (never split, or split and decoded again), those split but not at a
+ *           fixed point after the last launch, and the last of the 4 launches
+ *           between groups in which a group changed (0: none did).
+ *   scratch d_workspace, at least hpdct_decode_split_workspace_bytes(...)
+ *           bytes (hpdct_decode_scan's, 16 per interval and group and 64 per
+ *           segment more; -1 for arguments the call would refuse).  Eleven
+ *           launches in one chain with offsets, thirteen without; none depends
+ *           on a value the host reads, so the call can be captured into a graph.
+ *   speed   8192^2 noise at one MCU row per interval: 3.0 ms against
+ *           hpdct_decode_scan's 35.7; a 1080p noise frame without restart
+ *           markers 2.6 ms against 781.  The chain costs 2 ms whatever it
+ *           decodes, and short intervals run mostly idle workgroups: at 8 MCUs
+ *           per interval it is 60 times slower when every interval is split
+ *           (DESIGN.md 4.10), hence the threshold.
+ * The checks and their errors are hpdct_decode_scan's. */
+typedef struct hpdct_decode_split_info { /* written by the device; 8-byte aligned */
+    uint32_t bad_intervals, markers_found, marker_errors, reserved; /* as hpdct_decode_info */
+    uint32_t split_intervals;     /* intervals cut into segments */
+    uint32_t serial_intervals;    /* intervals walked by one lane: never split, or decoded again */
+    uint32_t unsettled_intervals; /* split, but not at a fixed point after the last launch */
+    uint32_t rounds;              /* the last launch between groups that changed a group's entry */
+} hpdct_decode_split_info;
+hpdct_status hpdct_decode_scan_split(const uint8_t* d_scan, int64_t bytes,
+                                     const uint64_t* d_interval_offsets /* or NULL */, int16_t* d_y, int16_t* d_cb,
+                                     int16_t* d_cr, int64_t height, int64_t width, hpdct_subsampling sub,
+                                     int64_t restart_interval, unsigned flags, int64_t split_min_bytes,
+                                     hpdct_decode_split_info* d_info, uint64_t* d_interval_status /* or NULL */,
+                                     void* d_workspace, int64_t workspace_bytes, void* stream);
+int64_t hpdct_decode_split_workspace_bytes(int64_t height, int64_t width, int components, hpdct_subsampling sub,
+                                           int64_t restart_interval, int64_t scan_bytes); /* host; -1 if refused */
+/* the bytes of a segment, the segments of a group, the launches between groups (host) */
+void hpdct_decode_split_geometry(int* segment_bytes, int* group_segments, int* rounds);
 /* The header of a baseline file (host only), the inverse of hpdct_jpeg_header:
  * walks SOI .. SOS of h_file[0 .. bytes) and never reads outside it.  APPn and
  * COM segments are skipped; a DQT or DHT segment may hold one table or several.
