@@ -77,6 +77,9 @@ enum : unsigned {
     kScanNatural = 1u << 25,  // the blocks are row-major inside (HPDCT_BLOCKS_NATURAL): permuted on load
     kScanEmit = 1u << 28,     // scan_code_kernel: the emit launch (clear: the measure launch)
     kScanOffsets = 1u << 29,  // scan_offsets_kernel
+    kScanTables = 1u << 27,   // scan_code_tables_kernel, unscan_decode_tables_kernel: the caller's Huffman tables
+                              // (a HuffBlob in device memory) instead of Annex K's
+    kScanHist = 1u << 30,     // scan_hist_kernel (hpdct_scan_hist.hpp)
 };
 // the entropy decoder's own variant bits (hpdct_unscan.hpp; its decode kernel also reads kScanNatural:
 // permuted on store)

@@ -355,16 +355,30 @@ inline Choice inverse_rgb(const RgbCall& c) {
 // lanes' own words 13,568 and its bit buffer 13,288); beyond
 // kScanMaxWgs intervals a workgroup takes every kScanMaxWgs-th one.  The
 // offsets launch is one 1024-thread workgroup.  hpdct_set_mapping is not read.
+// Under the caller's tables (tables: scan_code_tables_kernel) the same launches,
+// a wave's lanes' words 14,080 and its bit buffer 13,328 bytes (a block of 1665 bits).
 struct ScanCall {
     uint32_t intervals = 1;
     bool natural = false;
+    bool tables = false;
 };
 constexpr uint32_t kScanMaxWgs = 1u << 20;
 inline Choice scan_code(const ScanCall& c, bool emit) {
-    return {Family::kScan, with_block<64>((c.natural ? kScanNatural : 0u) | (emit ? kScanEmit : 0u)), 64u, 0u,
-            c.intervals < kScanMaxWgs ? c.intervals : kScanMaxWgs, 1u};
+    return {Family::kScan,
+            with_block<64>((c.natural ? kScanNatural : 0u) | (emit ? kScanEmit : 0u) | (c.tables ? kScanTables : 0u)),
+            64u, 0u, c.intervals < kScanMaxWgs ? c.intervals : kScanMaxWgs, 1u};
 }
 inline Choice scan_offsets() { return {Family::kScan, with_block<1024>(kScanOffsets), 1024u, 0u, 1u, 1u}; }
+// The statistics pass (hpdct_scan_hist.hpp): one lane per block in 256-thread
+// workgroups, a grid-stride loop under a cap of kScanHistMaxWgs workgroups (8
+// per CU of 256), so that the 1024-bin flush of a workgroup is paid once per
+// 256 blocks at most.  It does not read restart_interval beyond the DC predecessor.
+constexpr uint32_t kScanHistMaxWgs = 2048;
+inline Choice scan_hist(uint64_t blocks, bool natural) {
+    const uint64_t wgs = (blocks + 255u) / 256u;
+    return {Family::kScan, with_block<256>(kScanHist | (natural ? kScanNatural : 0u)), 256u, 0u,
+            wgs < kScanHistMaxWgs ? static_cast<uint32_t>(wgs < 1u ? 1u : wgs) : kScanHistMaxWgs, 1u};
+}
 
 // The entropy decoder (hpdct_unscan.hpp).  Huffman decoding is serial inside a
 // restart interval: one LANE walks one interval, in one-wave workgroups (the
@@ -389,6 +403,7 @@ inline Choice scan_offsets() { return {Family::kScan, with_block<1024>(kScanOffs
 struct UnscanCall {
     uint32_t intervals = 1;
     bool natural = false;
+    bool tables = false;  // unscan_decode_tables_kernel: the caller's tables (3,648 bytes of LDS instead of 3,280)
 };
 constexpr uint32_t kUnscanMaxWgs = 8192;
 constexpr uint32_t kUnscanChunkBytes = 4096;
@@ -400,8 +415,8 @@ inline Choice unscan_decode(const UnscanCall& c) {
     const uint32_t lanes = unscan_lanes(c.intervals);
     const uint32_t wgs = c.intervals / lanes + (c.intervals % lanes != 0u);
     const unsigned bit = lanes == 16u ? kUnscanLanes16 : lanes == 4u ? kUnscanLanes4 : lanes == 1u ? kUnscanLanes1 : 0u;
-    return {Family::kUnscan, with_block<64>((c.natural ? kScanNatural : 0u) | bit), 64u, 0u,
-            wgs < kUnscanMaxWgs ? wgs : kUnscanMaxWgs, 1u};
+    return {Family::kUnscan, with_block<64>((c.natural ? kScanNatural : 0u) | bit | (c.tables ? kScanTables : 0u)), 64u,
+            0u, wgs < kUnscanMaxWgs ? wgs : kUnscanMaxWgs, 1u};
 }
 // chunks: ceil(scan bytes / kUnscanChunkBytes), at least 1
 inline Choice unscan_locate(uint64_t chunks, bool place) {
@@ -453,8 +468,13 @@ inline Choice unsplit_groups(uint64_t groups, unsigned kind, bool natural) {
     return {Family::kUnsplit, with_block<256>(kind | (natural ? kScanNatural : 0u)), 256u, 0u,
             groups < kUnsplitMaxWgs ? static_cast<uint32_t>(groups < 1u ? 1u : groups) : kUnsplitMaxWgs, 1u};
 }
-inline Choice unsplit_settle(uint64_t groups) { return unsplit_groups(groups, kUnsplitSettle, false); }
-inline Choice unsplit_write(uint64_t groups, bool natural) { return unsplit_groups(groups, kUnsplitWrite, natural); }
+// tables: the kernels that stage the caller's tables (unsplit_*_tables_kernel), the same launches
+inline Choice unsplit_settle(uint64_t groups, bool tables = false) {
+    return unsplit_groups(groups, kUnsplitSettle | (tables ? kScanTables : 0u), false);
+}
+inline Choice unsplit_write(uint64_t groups, bool natural, bool tables = false) {
+    return unsplit_groups(groups, kUnsplitWrite | (tables ? kScanTables : 0u), natural);
+}
 // one workgroup per interval
 inline Choice unsplit_offsets(uint32_t intervals) { return unsplit_groups(intervals, kUnsplitOffsets, false); }
 // units: 16-byte pieces of all the frame's blocks, one per lane

@@ -153,6 +153,17 @@ constexpr uint32_t kBlkStride = 33;  // dwords per staged block: 32 + 1, so the 
 constexpr uint32_t kPrivStride = (kMaxBlockBits + 31) / 32 + 1;
 static_assert(kPrivStride % 2u == 1u, "odd stride");
 
+// Under a caller's tables (hpdct_encode_scan_tables) a code has up to 16 bits
+// in every table: a block reaches (16 + 11) + 63 * (16 + 10) = 1665 bits.
+constexpr int kMaxBlockBitsT = (16 + kMaxDcCat) + 63 * (16 + kMaxAcCat);
+static_assert(kMaxBlockBitsT == 1665, "16-bit codes");
+// hpdct_scan_bound_tables: 2 * 1665 / 8 = 416.25 bytes a block, rounded up
+constexpr int64_t kBoundPerBlockT = (2 * kMaxBlockBitsT + 7) / 8;
+static_assert(kBoundPerBlockT == 417, "rounded up");
+constexpr uint32_t kBitWordsT = (64u * kMaxBlockBitsT + 7u + 31u) / 32u + 1u;  // 3332 words
+constexpr uint32_t kPrivStrideT = (kMaxBlockBitsT + 31) / 32 + 2;              // 53 words and two: 55, odd
+static_assert(kPrivStrideT % 2u == 1u && kPrivStrideT > (kMaxBlockBitsT + 31) / 32, "odd stride");
+
 }  // namespace scan
 
 // The three launches on s, as policy::scan_code / scan_offsets choose them
@@ -162,6 +173,14 @@ static_assert(kPrivStride % 2u == 1u, "odd stride");
 hipError_t launch_scan(const int16_t* y, const int16_t* cb, const int16_t* cr, const scan::ScanGrid& g, bool natural,
                        uint8_t* out, uint64_t capacity, hpdct_scan_info* info, uint64_t* user_offs, void* workspace,
                        hipStream_t s);
+// the same under the caller's tables: d_tables a HuffBlob (hpdct_unscan.hpp) in
+// device memory, of which the coder reads the leading scan::CodeTables
+hipError_t launch_scan_tables(const int16_t* y, const int16_t* cb, const int16_t* cr, const scan::ScanGrid& g,
+                              bool natural, uint8_t* out, uint64_t capacity, hpdct_scan_info* info,
+                              uint64_t* user_offs, void* workspace, const void* d_tables, hipStream_t s);
+// hpdct_scan_histogram (hpdct_scan_hist.hpp): a memset of counts (4 * 256 uint64) and one launch
+hipError_t launch_scan_hist(const int16_t* y, const int16_t* cb, const int16_t* cr, const scan::ScanGrid& g,
+                            bool natural, uint64_t* counts, hipStream_t s);
 
 }  // namespace hpdct
 
@@ -200,12 +219,21 @@ __device__ inline void scan_or_bits(uint32_t* bits, uint32_t pos, uint32_t val, 
 // into priv (the lane's own kPrivStride words: no other lane touches them); the
 // last word's unused low bits are 0.  Returns the block's bit length
 // (<= kMaxBlockBits); oor counts the coefficients baseline cannot code.
+// kCustom: the tables are a caller's, untrusted: a length is clamped to 16 (so a
+// put takes at most 16 + 11 = 27 bits and the block at most kMaxBlockBitsT), and
+// a symbol without a code (length 0) is counted in oor as well.
+template <bool kCustom = false>
 __device__ inline uint32_t scan_walk(const uint32_t* blk, uint64_t nz, int dc, const uint32_t* ac,
                                      const uint32_t* dc_tab, uint32_t* priv, uint32_t& oor) {
     uint64_t acc = 0;           // the low nacc bits are pending
     uint32_t nacc = 0, nw = 0;  // nacc < 32 between puts
     auto put = [&](uint32_t entry, uint32_t cat, uint32_t extra) {
-        const uint32_t n = (entry >> 16) + cat;  // 1..26
+        uint32_t clen = entry >> 16;
+        if constexpr (kCustom) {
+            clen = clen > 16u ? 16u : clen;
+            oor += clen == 0u;
+        }
+        const uint32_t n = clen + cat;  // 1..26; kCustom: 0..27, and nacc + n <= 58 bits of acc
         acc = (acc << n) | (((entry & 0xffffu) << cat) | extra);
         nacc += n;
         if (nacc >= 32u) {
@@ -291,29 +319,33 @@ __device__ inline ScanBlockRef scan_locate(const int16_t* y, const int16_t* cb, 
 //   measure: lens[i] = the byte length of interval i, oor[i] its uncodable coefficients
 //   emit:    lens[i] holds the interval's byte offset (the offsets kernel ran);
 //            the bytes go to out, below capacity only, and only if !info->truncated
+// kVar with kScanTables: tab_src is the caller's (untrusted) tables and the
+// buffers are sized for blocks of kMaxBlockBitsT bits; else Annex K's.
 template <unsigned kVar>
-__global__ __launch_bounds__(64) void scan_code_kernel(const int16_t* __restrict__ y, const int16_t* __restrict__ cb,
-                                                       const int16_t* __restrict__ cr, const scan::ScanGrid g,
-                                                       uint64_t* __restrict__ lens, uint32_t* __restrict__ oor,
-                                                       const hpdct_scan_info* __restrict__ info,
-                                                       uint8_t* __restrict__ out, const uint64_t capacity) {
+__device__ inline void scan_code_body(const int16_t* __restrict__ y, const int16_t* __restrict__ cb,
+                                      const int16_t* __restrict__ cr, const scan::ScanGrid& g,
+                                      uint64_t* __restrict__ lens, uint32_t* __restrict__ oor,
+                                      const hpdct_scan_info* __restrict__ info, uint8_t* __restrict__ out,
+                                      const uint64_t capacity, const uint32_t* __restrict__ tab_src) {
     constexpr bool kEmit = (kVar & kScanEmit) != 0u;
     constexpr bool kNatural = (kVar & kScanNatural) != 0u;
+    constexpr bool kCustom = (kVar & kScanTables) != 0u;
+    constexpr uint32_t kPriv = kCustom ? scan::kPrivStrideT : scan::kPrivStride;
+    constexpr uint32_t kBits = kCustom ? scan::kBitWordsT : scan::kBitWords;
     __shared__ uint32_t s_tab[scan::kCodeTableWords];
     __shared__ uint32_t s_blk[64u * scan::kBlkStride];
-    __shared__ uint32_t s_priv[64u * scan::kPrivStride];
-    __shared__ uint32_t s_bits[scan::kBitWords];
+    __shared__ uint32_t s_priv[64u * kPriv];
+    __shared__ uint32_t s_bits[kBits];
     const uint32_t lane = threadIdx.x;
     if constexpr (kEmit) {
         if (info->truncated != 0u) return;
     }
     {
-        const uint32_t* src = &kScanCodeTables.ac[0][0];
         static_assert(sizeof(scan::CodeTables) == 4u * scan::kCodeTableWords, "tables are packed");
-        for (uint32_t i = lane; i < static_cast<uint32_t>(scan::kCodeTableWords); i += 64u) s_tab[i] = src[i];
+        for (uint32_t i = lane; i < static_cast<uint32_t>(scan::kCodeTableWords); i += 64u) s_tab[i] = tab_src[i];
     }
     uint32_t* const my_blk = s_blk + lane * scan::kBlkStride;
-    uint32_t* const my_priv = s_priv + lane * scan::kPrivStride;
+    uint32_t* const my_priv = s_priv + lane * kPriv;
 
     for (uint64_t iv = blockIdx.x; iv < g.intervals; iv += gridDim.x) {
         const uint64_t m0 = iv * g.per_interval;
@@ -336,6 +368,7 @@ __global__ __launch_bounds__(64) void scan_code_kernel(const int16_t* __restrict
             if (active) {
                 const ScanBlockRef r = scan_locate(y, cb, cr, g, m0, j);
                 chroma = r.chroma;
+                // the load and permutation below are also scan_stage of hpdct_scan_hist.hpp: keep the two in step
                 uint32_t v[32];
                 const uint4* p = reinterpret_cast<const uint4*>(r.blk);
 #pragma unroll
@@ -362,10 +395,10 @@ __global__ __launch_bounds__(64) void scan_code_kernel(const int16_t* __restrict
             }
             const uint32_t* ac = s_tab + 256u * chroma;
             const uint32_t* dct = s_tab + 512u + 16u * chroma;
-            const uint32_t len = active ? scan_walk(my_blk, nz, dcdiff, ac, dct, my_priv, oor_acc) : 0u;
+            const uint32_t len = active ? scan_walk<kCustom>(my_blk, nz, dcdiff, ac, dct, my_priv, oor_acc) : 0u;
             const uint32_t incl = scan_wave_prefix(len, lane);
             const uint32_t nbits = carry_n + __shfl(incl, 63, 64);
-            const uint32_t words = (nbits + 31u) / 32u + 1u;  // <= kBitWords
+            const uint32_t words = (nbits + 31u) / 32u + 1u;  // <= kBits
             for (uint32_t i = lane; i < words; i += 64u) s_bits[i] = 0u;
             __syncthreads();
             if (lane == 0u && carry_n != 0u) atomicOr(&s_bits[0], carry_v << (32u - carry_n));
@@ -424,6 +457,26 @@ __global__ __launch_bounds__(64) void scan_code_kernel(const int16_t* __restrict
             }
         }
     }
+}
+
+template <unsigned kVar>
+__global__ __launch_bounds__(64) void scan_code_kernel(const int16_t* __restrict__ y, const int16_t* __restrict__ cb,
+                                                       const int16_t* __restrict__ cr, const scan::ScanGrid g,
+                                                       uint64_t* __restrict__ lens, uint32_t* __restrict__ oor,
+                                                       const hpdct_scan_info* __restrict__ info,
+                                                       uint8_t* __restrict__ out, const uint64_t capacity) {
+    static_assert((kVar & kScanTables) == 0u, "Annex K");
+    scan_code_body<kVar>(y, cb, cr, g, lens, oor, info, out, capacity, &kScanCodeTables.ac[0][0]);
+}
+// the same under the caller's tables (kVar carries kScanTables): tables, the leading scan::CodeTables of a HuffBlob
+template <unsigned kVar>
+__global__ __launch_bounds__(64) void scan_code_tables_kernel(
+    const int16_t* __restrict__ y, const int16_t* __restrict__ cb, const int16_t* __restrict__ cr,
+    const scan::ScanGrid g, uint64_t* __restrict__ lens, uint32_t* __restrict__ oor,
+    const hpdct_scan_info* __restrict__ info, uint8_t* __restrict__ out, const uint64_t capacity,
+    const uint32_t* __restrict__ tables) {
+    static_assert((kVar & kScanTables) != 0u, "the caller's tables");
+    scan_code_body<kVar>(y, cb, cr, g, lens, oor, info, out, capacity, tables);
 }
 
 // Launch 2, one workgroup of 1024 threads: lens[i] (byte lengths) becomes the

@@ -28,6 +28,8 @@
 
 #include <stdint.h>
 
+#include <type_traits>
+
 #include "hpdct.h"
 #include "hpdct_kernels.h"
 #include "hpdct_scan.hpp"
@@ -80,6 +82,26 @@ constexpr DecodeTables make_decode_tables() {
     for (int kind = 0; kind < 4; ++kind) fill_decode(scan::spec_of(kind), t, kind);
     return t;
 }
+
+// The same tables for a caller's DHT (hpdct_huffman.hpp fills them): room for
+// 256 symbols a table.  Their contents are the caller's data, so the walk masks
+// the one index it forms from them (kUntrusted below) and clamps their lengths.
+struct DecodeTablesWide {
+    uint16_t look[4][256];
+    int32_t maxcode[4][18];
+    int32_t valoff[4][18];
+    uint8_t vals[4][256];
+};
+static_assert(sizeof(DecodeTablesWide) == 3648u, "tables are packed");
+// what hpdct_huffman_prepare writes and the *_tables calls read: the coder's
+// entries (scan::CodeTables), then the decoder's tables
+struct HuffBlob {
+    scan::CodeTables code;
+    DecodeTablesWide dec;
+};
+static_assert(sizeof(HuffBlob) == 5824u && sizeof(HuffBlob) % 16u == 0u, "the blob is packed");
+template <class Tab>
+constexpr bool kUntrusted = std::is_same_v<Tab, DecodeTablesWide>;
 
 // The workspace: the byte position of the j-th marker for j < intervals
 // (uint64), then a uint64 per 4096-byte chunk of the scan (its marker count,
@@ -183,7 +205,8 @@ HPDCT_HD void fill(Reader& r) {
 // code is matched against the 16 bits ahead (zeros beyond the fetched ones); a
 // match longer than what was fetched, or none, is the fetch's error, as it is
 // for a reader that takes one bit at a time: a code is never a prefix of another.
-HPDCT_HD uint32_t symbol(Reader& r, const DecodeTables* t, uint32_t kind, uint32_t& sym) {
+template <class Tab>
+HPDCT_HD uint32_t symbol(Reader& r, const Tab* t, uint32_t kind, uint32_t& sym) {
     fill(r);
     const uint32_t peek = static_cast<uint32_t>(r.acc >> 48);
     const uint32_t e = t->look[kind][peek >> 8];
@@ -195,7 +218,10 @@ HPDCT_HD uint32_t symbol(Reader& r, const DecodeTables* t, uint32_t kind, uint32
             const int32_t code = static_cast<int32_t>(peek >> (16u - l));
             if (code <= t->maxcode[kind][l]) {
                 len = l;
-                sym = t->vals[kind][code + t->valoff[kind][l]];
+                if constexpr (kUntrusted<Tab>)
+                    sym = t->vals[kind][(static_cast<uint32_t>(code) + static_cast<uint32_t>(t->valoff[kind][l])) & 255u];
+                else
+                    sym = t->vals[kind][code + t->valoff[kind][l]];
                 break;
             }
         }
@@ -245,9 +271,10 @@ HPDCT_HD void store_block(int16_t* dst, uint32_t* row) {
 // nullptr with g.bpm == 1) and returns the status.  row: 32 dwords of the
 // caller's, for this walk alone.  kNatural: a block's coefficient n is stored
 // at zigzag::kOrder[n].  Every block of the interval is written exactly once.
-template <bool kNatural>
+// Tab: DecodeTables (Annex K) or DecodeTablesWide (the caller's, untrusted).
+template <bool kNatural, class Tab = DecodeTables>
 HPDCT_HD uint64_t walk_interval(const uint8_t* scan, uint64_t lo, uint64_t hi, uint32_t pre, uint64_t iv,
-                                const scan::ScanGrid& g, const DecodeTables* t, const uint8_t* order, uint32_t* row,
+                                const scan::ScanGrid& g, const Tab* t, const uint8_t* order, uint32_t* row,
                                 int16_t* y, int16_t* cb, int16_t* cr) {
     const uint64_t m0 = iv * g.per_interval;
     const uint64_t mcount = g.nmcu - m0 < g.per_interval ? g.nmcu - m0 : g.per_interval;
@@ -270,6 +297,7 @@ HPDCT_HD uint64_t walk_interval(const uint8_t* scan, uint64_t lo, uint64_t hi, u
             code = symbol(r, t, chroma, sym);
             if (code != kOk) break;
             int32_t diff;
+            if constexpr (kUntrusted<Tab>) sym &= 15u;  // hpdct_huffman_prepare refuses a DC symbol above 15
             code = extra(r, sym, diff);
             if (code != kOk) break;
             const int32_t pred = (comp == 0u ? pred0 : comp == 1u ? pred1 : pred2) + diff;
@@ -338,6 +366,10 @@ HPDCT_HD uint64_t walk_interval(const uint8_t* scan, uint64_t lo, uint64_t hi, u
 hipError_t launch_unscan(const uint8_t* scan, uint64_t bytes, const uint64_t* offs, int16_t* y, int16_t* cb,
                          int16_t* cr, const scan::ScanGrid& g, bool natural, hpdct_decode_info* info, uint64_t* status,
                          void* workspace, hipStream_t s);
+// the same under the caller's tables: d_tables a HuffBlob in device memory
+hipError_t launch_unscan_tables(const uint8_t* scan, uint64_t bytes, const uint64_t* offs, int16_t* y, int16_t* cb,
+                                int16_t* cr, const scan::ScanGrid& g, bool natural, hpdct_decode_info* info,
+                                uint64_t* status, void* workspace, const void* d_tables, hipStream_t s);
 // the marker search's launches alone (count, rank, place; the rank launch alone with offsets), for hpdct_unscan_split.hpp
 hipError_t launch_unscan_locate(const uint8_t* scan, uint64_t bytes, const uint64_t* offs, const scan::ScanGrid& g,
                                 hpdct_decode_info* info, void* workspace, hipStream_t s);
@@ -450,27 +482,27 @@ __global__ __launch_bounds__(1024) void unscan_rank_kernel(uint64_t* __restrict_
 // Launch 4; one wave per workgroup, its first kLanes lanes take an interval
 // each: workgroup b the intervals b * kLanes + lane, then every gridDim.x-th
 // such group.  offs != nullptr: the caller's table; else mpos and
-// info->markers_found, as the launches before wrote them.
-template <unsigned kVar>
-__global__ __launch_bounds__(64) void unscan_decode_kernel(const uint8_t* __restrict__ scan, const uint64_t bytes,
-                                                           const uint64_t* __restrict__ offs,
-                                                           const uint64_t* __restrict__ mpos, int16_t* __restrict__ y,
-                                                           int16_t* __restrict__ cb, int16_t* __restrict__ cr,
-                                                           const scan::ScanGrid g, hpdct_decode_info* __restrict__ info,
-                                                           uint64_t* __restrict__ status) {
+// info->markers_found, as the launches before wrote them.  Tab and tab_src: the
+// tables' type and where they are staged from (sizeof(Tab) bytes, 4-byte aligned).
+template <unsigned kVar, class Tab>
+__device__ inline void unscan_decode_body(const uint8_t* __restrict__ scan, const uint64_t bytes,
+                                          const uint64_t* __restrict__ offs, const uint64_t* __restrict__ mpos,
+                                          int16_t* __restrict__ y, int16_t* __restrict__ cb, int16_t* __restrict__ cr,
+                                          const scan::ScanGrid& g, hpdct_decode_info* __restrict__ info,
+                                          uint64_t* __restrict__ status, const uint32_t* __restrict__ tab_src) {
     constexpr uint32_t kLanes = unscan_lanes_of(kVar);
     constexpr bool kNatural = (kVar & kScanNatural) != 0u;
-    __shared__ uint32_t s_tab[unscan::kTableWords];
+    constexpr uint32_t kWords = static_cast<uint32_t>(sizeof(Tab) / 4u);
+    __shared__ uint32_t s_tab[kWords];
     __shared__ uint32_t s_row[kLanes * scan::kBlkStride];
     __shared__ uint8_t s_order[64];
     const uint32_t lane = threadIdx.x;
     {
-        const uint32_t* src = reinterpret_cast<const uint32_t*>(&kUnscanTables);
-        for (uint32_t i = lane; i < static_cast<uint32_t>(unscan::kTableWords); i += 64u) s_tab[i] = src[i];
+        for (uint32_t i = lane; i < kWords; i += 64u) s_tab[i] = tab_src[i];
         s_order[lane] = kUnscanOrder.v[lane];
     }
     __syncthreads();
-    const unscan::DecodeTables* tab = reinterpret_cast<const unscan::DecodeTables*>(s_tab);
+    const Tab* tab = reinterpret_cast<const Tab*>(s_tab);
     const uint64_t found = offs ? 0u : info->markers_found;
     uint32_t bad = 0;
     for (uint64_t base = static_cast<uint64_t>(blockIdx.x) * kLanes; base < g.intervals;
@@ -488,6 +520,27 @@ __global__ __launch_bounds__(64) void unscan_decode_kernel(const uint8_t* __rest
     }
     bad = unscan_wave_sum(bad);
     if (lane == 0u && bad != 0u) atomicAdd(&info->bad_intervals, bad);  // integer: order-independent
+}
+template <unsigned kVar>
+__global__ __launch_bounds__(64) void unscan_decode_kernel(const uint8_t* __restrict__ scan, const uint64_t bytes,
+                                                           const uint64_t* __restrict__ offs,
+                                                           const uint64_t* __restrict__ mpos, int16_t* __restrict__ y,
+                                                           int16_t* __restrict__ cb, int16_t* __restrict__ cr,
+                                                           const scan::ScanGrid g, hpdct_decode_info* __restrict__ info,
+                                                           uint64_t* __restrict__ status) {
+    static_assert(sizeof(unscan::DecodeTables) == 4u * unscan::kTableWords, "tables are packed");
+    unscan_decode_body<kVar, unscan::DecodeTables>(scan, bytes, offs, mpos, y, cb, cr, g, info, status,
+                                                   reinterpret_cast<const uint32_t*>(&kUnscanTables));
+}
+// the same under the caller's tables (kVar carries kScanTables): blob, a HuffBlob in device memory
+template <unsigned kVar>
+__global__ __launch_bounds__(64) void unscan_decode_tables_kernel(
+    const uint8_t* __restrict__ scan, const uint64_t bytes, const uint64_t* __restrict__ offs,
+    const uint64_t* __restrict__ mpos, int16_t* __restrict__ y, int16_t* __restrict__ cb, int16_t* __restrict__ cr,
+    const scan::ScanGrid g, hpdct_decode_info* __restrict__ info, uint64_t* __restrict__ status,
+    const unscan::HuffBlob* __restrict__ blob) {
+    unscan_decode_body<kVar, unscan::DecodeTablesWide>(scan, bytes, offs, mpos, y, cb, cr, g, info, status,
+                                                       reinterpret_cast<const uint32_t*>(&blob->dec));
 }
 
 }  // namespace hpdct

@@ -40,10 +40,14 @@ __device__ inline uint64_t blocks_of(const scan::ScanGrid& g, uint64_t iv) {
     const uint64_t m0 = iv * g.per_interval;
     return (g.nmcu - m0 < g.per_interval ? g.nmcu - m0 : g.per_interval) * g.bpm;
 }
-template <uint32_t kThreads>
-__device__ inline void stage_tables(uint32_t* s_tab) {
-    const uint32_t* src = reinterpret_cast<const uint32_t*>(&kUnsplitTables);
-    for (uint32_t i = threadIdx.x; i < static_cast<uint32_t>(unscan::kTableWords); i += kThreads) s_tab[i] = src[i];
+// Tab's words from src (the built-in tables, or the decoder's part of a caller's blob) to LDS
+template <uint32_t kThreads, class Tab>
+__device__ inline void stage_tables(uint32_t* s_tab, const uint32_t* __restrict__ src) {
+    for (uint32_t i = threadIdx.x; i < static_cast<uint32_t>(sizeof(Tab) / 4u); i += kThreads) s_tab[i] = src[i];
+}
+__device__ inline const uint32_t* builtin_tables() { return reinterpret_cast<const uint32_t*>(&kUnsplitTables); }
+__device__ inline const uint32_t* blob_tables(const unscan::HuffBlob* blob) {
+    return reinterpret_cast<const uint32_t*>(&blob->dec);
 }
 
 // The plan, one workgroup of 1024 threads; thread t owns the intervals [t * per, (t + 1) * per).  An interval's
@@ -120,14 +124,17 @@ __device__ inline GroupAt group_at(const Call& c, const Ws& ws, uint64_t found, 
 }
 
 // The settle launches; `launch` is 0 .. kRounds.  Workgroup w takes the groups w, w + gridDim.x, ...
-__global__ __launch_bounds__(256) void unsplit_settle_kernel(const Call c, const Ws ws, const uint32_t launch,
-                                                             hpdct_decode_split_info* __restrict__ info) {
-    __shared__ uint32_t s_tab[unscan::kTableWords];
+// Tab and src: the tables' type and where they are staged from.
+template <class Tab>
+__device__ inline void unsplit_settle_body(const Call& c, const Ws& ws, const uint32_t launch,
+                                           hpdct_decode_split_info* __restrict__ info,
+                                           const uint32_t* __restrict__ src) {
+    __shared__ uint32_t s_tab[sizeof(Tab) / 4u];
     __shared__ SegState s_ex[kG];
     const uint32_t t = threadIdx.x;
-    stage_tables<kG>(s_tab);
+    stage_tables<kG, Tab>(s_tab, src);
     __syncthreads();
-    const unscan::DecodeTables* tab = reinterpret_cast<const unscan::DecodeTables*>(s_tab);
+    const Tab* tab = reinterpret_cast<const Tab*>(s_tab);
     const uint64_t found = c.offs ? 0u : info->markers_found, groups = ws.totals[0];
     const SegState* last_in = ws.glast + ((launch + 1u) & 1u) * ws.ngrp;
     SegState* last_out = ws.glast + (launch & 1u) * ws.ngrp;
@@ -186,6 +193,16 @@ __global__ __launch_bounds__(256) void unsplit_settle_kernel(const Call c, const
             if (t == a.n - 1u) last_out[grp] = ex;
         }
     }
+}
+
+__global__ __launch_bounds__(256) void unsplit_settle_kernel(const Call c, const Ws ws, const uint32_t launch,
+                                                             hpdct_decode_split_info* __restrict__ info) {
+    unsplit_settle_body<unscan::DecodeTables>(c, ws, launch, info, builtin_tables());
+}
+__global__ __launch_bounds__(256) void unsplit_settle_tables_kernel(const Call c, const Ws ws, const uint32_t launch,
+                                                                    hpdct_decode_split_info* __restrict__ info,
+                                                                    const unscan::HuffBlob* __restrict__ blob) {
+    unsplit_settle_body<unscan::DecodeTablesWide>(c, ws, launch, info, blob_tables(blob));
 }
 
 // The offsets launch: workgroup w takes the intervals w, w + gridDim.x, ...; thread t the segments
@@ -270,18 +287,19 @@ __global__ __launch_bounds__(256) void unsplit_clear_kernel(const Ws ws, int16_t
 
 // The write launch: the groups as the settle launches take them; a lane of an interval that passed walks its
 // segment from the entry the fixed point gives it and stores what it decodes.
-template <unsigned kVar>
-__global__ __launch_bounds__(256) void unsplit_write_kernel(const Call c, const Ws ws, int16_t* __restrict__ y,
-                                                            int16_t* __restrict__ cb, int16_t* __restrict__ cr,
-                                                            const hpdct_decode_split_info* __restrict__ info) {
+template <unsigned kVar, class Tab>
+__device__ inline void unsplit_write_body(const Call& c, const Ws& ws, int16_t* __restrict__ y,
+                                          int16_t* __restrict__ cb, int16_t* __restrict__ cr,
+                                          const hpdct_decode_split_info* __restrict__ info,
+                                          const uint32_t* __restrict__ src) {
     constexpr bool kNatural = (kVar & kScanNatural) != 0u;
-    __shared__ uint32_t s_tab[unscan::kTableWords];
+    __shared__ uint32_t s_tab[sizeof(Tab) / 4u];
     __shared__ uint8_t s_order[64];
     const uint32_t t = threadIdx.x;
-    stage_tables<kG>(s_tab);
+    stage_tables<kG, Tab>(s_tab, src);
     if (t < 64u) s_order[t] = kUnsplitOrder.v[t];
     __syncthreads();
-    const unscan::DecodeTables* tab = reinterpret_cast<const unscan::DecodeTables*>(s_tab);
+    const Tab* tab = reinterpret_cast<const Tab*>(s_tab);
     const uint64_t found = c.offs ? 0u : info->markers_found, groups = ws.totals[0];
     for (uint64_t grp = blockIdx.x; grp < groups; grp += gridDim.x) {
         const GroupAt a = group_at(c, ws, found, grp);
@@ -302,23 +320,37 @@ __global__ __launch_bounds__(256) void unsplit_write_kernel(const Call c, const 
     }
 }
 
+template <unsigned kVar>
+__global__ __launch_bounds__(256) void unsplit_write_kernel(const Call c, const Ws ws, int16_t* __restrict__ y,
+                                                            int16_t* __restrict__ cb, int16_t* __restrict__ cr,
+                                                            const hpdct_decode_split_info* __restrict__ info) {
+    unsplit_write_body<kVar, unscan::DecodeTables>(c, ws, y, cb, cr, info, builtin_tables());
+}
+template <unsigned kVar>
+__global__ __launch_bounds__(256) void unsplit_write_tables_kernel(const Call c, const Ws ws, int16_t* __restrict__ y,
+                                                                   int16_t* __restrict__ cb, int16_t* __restrict__ cr,
+                                                                   const hpdct_decode_split_info* __restrict__ info,
+                                                                   const unscan::HuffBlob* __restrict__ blob) {
+    unsplit_write_body<kVar, unscan::DecodeTablesWide>(c, ws, y, cb, cr, info, blob_tables(blob));
+}
+
 // The serial launch: unscan_decode_kernel's shape; an interval that passed gets status 0, every other one
 // hpdct_unscan.hpp's walk, which writes all its blocks.
-template <unsigned kVar>
-__global__ __launch_bounds__(64) void unsplit_serial_kernel(const Call c, const Ws ws, int16_t* __restrict__ y,
-                                                            int16_t* __restrict__ cb, int16_t* __restrict__ cr,
-                                                            hpdct_decode_split_info* __restrict__ info,
-                                                            uint64_t* __restrict__ status) {
+template <unsigned kVar, class Tab>
+__device__ inline void unsplit_serial_body(const Call& c, const Ws& ws, int16_t* __restrict__ y,
+                                           int16_t* __restrict__ cb, int16_t* __restrict__ cr,
+                                           hpdct_decode_split_info* __restrict__ info, uint64_t* __restrict__ status,
+                                           const uint32_t* __restrict__ src) {
     constexpr uint32_t kLanes = unscan_lanes_of(kVar);
     constexpr bool kNatural = (kVar & kScanNatural) != 0u;
-    __shared__ uint32_t s_tab[unscan::kTableWords];
+    __shared__ uint32_t s_tab[sizeof(Tab) / 4u];
     __shared__ uint32_t s_row[kLanes * scan::kBlkStride];
     __shared__ uint8_t s_order[64];
     const uint32_t lane = threadIdx.x;
-    stage_tables<64>(s_tab);
+    stage_tables<64, Tab>(s_tab, src);
     s_order[lane] = kUnsplitOrder.v[lane];
     __syncthreads();
-    const unscan::DecodeTables* tab = reinterpret_cast<const unscan::DecodeTables*>(s_tab);
+    const Tab* tab = reinterpret_cast<const Tab*>(s_tab);
     const uint64_t found = c.offs ? 0u : info->markers_found;
     uint32_t bad = 0, serial = 0;
     for (uint64_t base = static_cast<uint64_t>(blockIdx.x) * kLanes; base < c.g.intervals;
@@ -342,11 +374,31 @@ __global__ __launch_bounds__(64) void unsplit_serial_kernel(const Call c, const 
     if (lane == 0u && serial != 0u) atomicAdd(&info->serial_intervals, serial);
 }
 
+template <unsigned kVar>
+__global__ __launch_bounds__(64) void unsplit_serial_kernel(const Call c, const Ws ws, int16_t* __restrict__ y,
+                                                            int16_t* __restrict__ cb, int16_t* __restrict__ cr,
+                                                            hpdct_decode_split_info* __restrict__ info,
+                                                            uint64_t* __restrict__ status) {
+    unsplit_serial_body<kVar, unscan::DecodeTables>(c, ws, y, cb, cr, info, status, builtin_tables());
+}
+template <unsigned kVar>
+__global__ __launch_bounds__(64) void unsplit_serial_tables_kernel(const Call c, const Ws ws, int16_t* __restrict__ y,
+                                                                   int16_t* __restrict__ cb, int16_t* __restrict__ cr,
+                                                                   hpdct_decode_split_info* __restrict__ info,
+                                                                   uint64_t* __restrict__ status,
+                                                                   const unscan::HuffBlob* __restrict__ blob) {
+    unsplit_serial_body<kVar, unscan::DecodeTablesWide>(c, ws, y, cb, cr, info, status, blob_tables(blob));
+}
+
+// blob == nullptr: Annex K's kernels
 template <unsigned kLaneBit>
 hipError_t launch_serial(const policy::Choice& ch, hipStream_t s, const Call& c, const Ws& ws, int16_t* y, int16_t* cb,
-                         int16_t* cr, hpdct_decode_split_info* info, uint64_t* status) {
+                         int16_t* cr, hpdct_decode_split_info* info, uint64_t* status, const unscan::HuffBlob* blob) {
     return policy::with_bit<kScanNatural, true>(ch.var, [&](auto kN) {
         constexpr unsigned kV = with_block<64>(kUnsplitSerial | decltype(kN)::value | kLaneBit);
+        if (blob)
+            return launch_choice<(kV | kScanTables), unsplit_serial_tables_kernel<(kV | kScanTables)>>(
+                ch, s, c, ws, y, cb, cr, info, status, blob);
         return launch_choice<kV, unsplit_serial_kernel<kV>>(ch, s, c, ws, y, cb, cr, info, status);
     });
 }
@@ -356,6 +408,17 @@ hipError_t launch_serial(const policy::Choice& ch, hipStream_t s, const Call& c,
 hipError_t launch_unscan_split(const uint8_t* scan, uint64_t bytes, const uint64_t* offs, int16_t* y, int16_t* cb,
                                int16_t* cr, const scan::ScanGrid& g, bool natural, uint64_t split_min,
                                hpdct_decode_split_info* info, uint64_t* status, void* workspace, hipStream_t s) {
+    return launch_unscan_split_tables(scan, bytes, offs, y, cb, cr, g, natural, split_min, info, status, workspace,
+                                      nullptr, s);
+}
+
+hipError_t launch_unscan_split_tables(const uint8_t* scan, uint64_t bytes, const uint64_t* offs, int16_t* y,
+                                      int16_t* cb, int16_t* cr, const scan::ScanGrid& g, bool natural,
+                                      uint64_t split_min, hpdct_decode_split_info* info, uint64_t* status,
+                                      void* workspace, const void* d_tables, hipStream_t s) {
+    const unscan::HuffBlob* blob = static_cast<const unscan::HuffBlob*>(d_tables);
+    const bool tables = blob != nullptr;
+    constexpr unsigned kSettleT = with_block<256>(kUnsplitSettle | kScanTables);
     if (hipError_t e = launch_unscan_locate(scan, bytes, offs, g, reinterpret_cast<hpdct_decode_info*>(info), workspace, s))
         return e;
     const unsplit::Layout lay = unsplit::layout(g.intervals, bytes);
@@ -365,8 +428,10 @@ hipError_t launch_unscan_split(const uint8_t* scan, uint64_t bytes, const uint64
     constexpr unsigned kOffsetsV = with_block<256>(kUnsplitOffsets), kClearV = with_block<256>(kUnsplitClear);
     if (hipError_t e = launch_choice<kPlanV, unsplit_plan_kernel>(policy::unsplit_plan(), s, c, ws, info)) return e;
     for (uint32_t launch = 0; launch <= unsplit::kRounds; ++launch)
-        if (hipError_t e = launch_choice<kSettleV, unsplit_settle_kernel>(policy::unsplit_settle(lay.ngrp), s, c, ws,
-                                                                          launch, info))
+        if (hipError_t e = tables ? launch_choice<kSettleT, unsplit_settle_tables_kernel>(
+                                        policy::unsplit_settle(lay.ngrp, true), s, c, ws, launch, info, blob)
+                                  : launch_choice<kSettleV, unsplit_settle_kernel>(policy::unsplit_settle(lay.ngrp), s, c,
+                                                                                   ws, launch, info))
             return e;
     if (hipError_t e = launch_choice<kOffsetsV, unsplit_offsets_kernel>(policy::unsplit_offsets(g.intervals), s, c, ws, info))
         return e;
@@ -374,20 +439,23 @@ hipError_t launch_unscan_split(const uint8_t* scan, uint64_t bytes, const uint64
     if (hipError_t e = launch_choice<kClearV, unsplit_clear_kernel>(policy::unsplit_clear(units), s, ws, y, cb, cr, g))
         return e;
     const hpdct_decode_split_info* cinfo = info;
-    const policy::Choice cw = policy::unsplit_write(lay.ngrp, natural);
+    const policy::Choice cw = policy::unsplit_write(lay.ngrp, natural, tables);
     if (hipError_t e = policy::with_bit<kScanNatural, true>(cw.var, [&](auto kN) {
             constexpr unsigned kV = with_block<256>(kUnsplitWrite | decltype(kN)::value);
+            if (tables)
+                return launch_choice<(kV | kScanTables), unsplit_write_tables_kernel<(kV | kScanTables)>>(
+                    cw, s, c, ws, y, cb, cr, cinfo, blob);
             return launch_choice<kV, unsplit_write_kernel<kV>>(cw, s, c, ws, y, cb, cr, cinfo);
         }))
         return e;
     policy::UnscanCall pc;
-    pc.intervals = g.intervals, pc.natural = natural;
+    pc.intervals = g.intervals, pc.natural = natural, pc.tables = tables;
     const policy::Choice cs = policy::unsplit_serial(pc);
     switch (unscan_lanes_of(cs.var)) {
-        case 1u: return launch_serial<kUnscanLanes1>(cs, s, c, ws, y, cb, cr, info, status);
-        case 4u: return launch_serial<kUnscanLanes4>(cs, s, c, ws, y, cb, cr, info, status);
-        case 16u: return launch_serial<kUnscanLanes16>(cs, s, c, ws, y, cb, cr, info, status);
-        default: return launch_serial<0u>(cs, s, c, ws, y, cb, cr, info, status);
+        case 1u: return launch_serial<kUnscanLanes1>(cs, s, c, ws, y, cb, cr, info, status, blob);
+        case 4u: return launch_serial<kUnscanLanes4>(cs, s, c, ws, y, cb, cr, info, status, blob);
+        case 16u: return launch_serial<kUnscanLanes16>(cs, s, c, ws, y, cb, cr, info, status, blob);
+        default: return launch_serial<0u>(cs, s, c, ws, y, cb, cr, info, status, blob);
     }
 }
 

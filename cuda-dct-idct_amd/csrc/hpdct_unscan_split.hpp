@@ -211,9 +211,10 @@ struct StoreSink {
 // the clean end of an interval, exit at hi without a flag.  Every turn consumes
 // at least a bit and starts before `end`, at most 8 * kSegBytes bits after the
 // entry: the loop's bound is never the reason it ends.
-template <class Sink>
+// Tab: unscan::DecodeTables (Annex K) or unscan::DecodeTablesWide (the caller's, untrusted).
+template <class Sink, class Tab>
 HPDCT_HD SegState walk_segment(const uint8_t* scan, uint64_t lo, uint64_t hi, uint64_t end, const SegState& entry,
-                               uint32_t bpm, const unscan::DecodeTables* t, Sink& sink) {
+                               uint32_t bpm, const Tab* t, Sink& sink) {
     using namespace unscan;
     if (entry.pos >= end) return entry_of(entry);  // a symbol of an earlier segment covers this one
     uint32_t kk = (entry.bits >> 3) & 7u, k = (entry.bits >> 6) & 127u, nblk = 0, flags = 0;
@@ -240,6 +241,7 @@ HPDCT_HD SegState walk_segment(const uint8_t* scan, uint64_t lo, uint64_t hi, ui
                     return SegState{hi, (kk << 3) | flags, nblk};
             }
             int32_t diff = 0;
+            if constexpr (kUntrusted<Tab>) sym &= 15u;  // hpdct_huffman_prepare refuses a DC symbol above 15
             if (code == kOk) code = extra(r, sym, diff);
             if (code == kOk) sink.dc(comp, diff), k = 1u;
         } else {
@@ -285,5 +287,10 @@ HPDCT_HD bool ends_clean(const SegState& last, uint64_t hi) { return last.pos ==
 hipError_t launch_unscan_split(const uint8_t* scan, uint64_t bytes, const uint64_t* offs, int16_t* y, int16_t* cb,
                                int16_t* cr, const scan::ScanGrid& g, bool natural, uint64_t split_min,
                                hpdct_decode_split_info* info, uint64_t* status, void* workspace, hipStream_t s);
+// the same under the caller's tables: d_tables a HuffBlob (hpdct_unscan.hpp) in device memory, or nullptr for Annex K
+hipError_t launch_unscan_split_tables(const uint8_t* scan, uint64_t bytes, const uint64_t* offs, int16_t* y,
+                                      int16_t* cb, int16_t* cr, const scan::ScanGrid& g, bool natural,
+                                      uint64_t split_min, hpdct_decode_split_info* info, uint64_t* status,
+                                      void* workspace, const void* d_tables, hipStream_t s);
 
 }  // namespace hpdct

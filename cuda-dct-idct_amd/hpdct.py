@@ -62,6 +62,10 @@ C_SYMBOLS = [
     "hpdct_huffman_table",
     "hpdct_decode_scan", "hpdct_decode_workspace_bytes", "hpdct_jpeg_parse",
     "hpdct_decode_scan_split", "hpdct_decode_split_workspace_bytes", "hpdct_decode_split_geometry",
+    "hpdct_huffman_blob_bytes", "hpdct_huffman_prepare", "hpdct_huffman_optimal", "hpdct_scan_histogram",
+    "hpdct_scan_bound_tables", "hpdct_encode_scan_tables", "hpdct_decode_scan_tables",
+    "hpdct_decode_scan_split_tables",
+    "hpdct_jpeg_header_tables", "hpdct_jpeg_parse_tables",
 ]
 MAPPINGS = {"auto": 0, "tile": 1, "octet": 2, "duo": 3}
 BASELINES = {"reference_3pass": 0, "fastappr_3pass": 1}
@@ -162,6 +166,26 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.hpdct_decode_split_geometry.restype = None
     lib.hpdct_jpeg_parse.argtypes = [vp, i64, vp]
     lib.hpdct_jpeg_parse.restype = ctypes.c_int
+    lib.hpdct_huffman_blob_bytes.argtypes = []
+    lib.hpdct_huffman_blob_bytes.restype = i64
+    lib.hpdct_huffman_prepare.argtypes = [vp, vp, i64]
+    lib.hpdct_huffman_prepare.restype = ctypes.c_int
+    lib.hpdct_huffman_optimal.argtypes = [vp, vp]
+    lib.hpdct_huffman_optimal.restype = ctypes.c_int
+    lib.hpdct_scan_histogram.argtypes = [vp, vp, vp, i64, i64, ctypes.c_int, i64, ctypes.c_uint, vp, vp]
+    lib.hpdct_scan_histogram.restype = ctypes.c_int
+    lib.hpdct_scan_bound_tables.argtypes = [i64, i64]
+    lib.hpdct_scan_bound_tables.restype = i64
+    lib.hpdct_encode_scan_tables.argtypes = lib.hpdct_encode_scan.argtypes[:-1] + [vp, vp]
+    lib.hpdct_encode_scan_tables.restype = ctypes.c_int
+    lib.hpdct_decode_scan_tables.argtypes = lib.hpdct_decode_scan.argtypes[:-1] + [vp, vp]
+    lib.hpdct_decode_scan_tables.restype = ctypes.c_int
+    lib.hpdct_decode_scan_split_tables.argtypes = lib.hpdct_decode_scan_split.argtypes[:-1] + [vp, vp]
+    lib.hpdct_decode_scan_split_tables.restype = ctypes.c_int
+    lib.hpdct_jpeg_header_tables.argtypes = lib.hpdct_jpeg_header.argtypes + [vp]
+    lib.hpdct_jpeg_header_tables.restype = ctypes.c_int
+    lib.hpdct_jpeg_parse_tables.argtypes = [vp, i64, vp, vp]
+    lib.hpdct_jpeg_parse_tables.restype = ctypes.c_int
     lib.hpdct_status_string.restype = ctypes.c_char_p
     lib.hpdct_status_string.argtypes = [ctypes.c_int]
     lib.hpdct_last_error_string.restype = ctypes.c_char_p
@@ -811,16 +835,91 @@ def huffman_table(kind):
     return bits, vals[:n.value].copy()
 
 
+class _HuffmanSpec(ctypes.Structure):  # hpdct_huffman_spec
+    _fields_ = [("bits", ctypes.c_uint8 * 16), ("vals", ctypes.c_uint8 * 256), ("nvals", ctypes.c_int32)]
+
+
+def _huffman_specs(specs):
+    """Four (bits, vals) pairs (None: an empty table) as hpdct_huffman_spec[4].  nvals is the length of vals:
+    whether it is the sum of bits is the library's to judge."""
+    if len(specs) != 4:
+        raise HpdctError(1, f"four Huffman tables are expected (DC luma, AC luma, DC chroma, AC chroma; got {len(specs)})")
+    arr = (_HuffmanSpec * 4)()
+    for k, sp in enumerate(specs):
+        if sp is None:
+            continue
+        bits, vals = (np.asarray(a, np.int64).ravel() for a in sp)
+        if bits.size != 16 or vals.size > 256 or bits.min(initial=0) < 0 or bits.max(initial=0) > 255 or \
+                vals.min(initial=0) < 0 or vals.max(initial=0) > 255:
+            raise HpdctError(1, f"table {k}: bits is 16 bytes and vals at most 256 bytes")
+        arr[k].bits[:] = [int(b) for b in bits]
+        arr[k].vals[:vals.size] = [int(v) for v in vals]
+        arr[k].nvals = int(vals.size)
+    return arr
+
+
+def _specs_out(arr):
+    return [(np.array(a.bits, np.uint8), np.array(a.vals, np.uint8)[:max(0, min(256, a.nvals))].copy()) for a in arr]
+
+
+def huffman_prepare(specs) -> np.ndarray:
+    """The table blob of four Huffman tables (hpdct_huffman_prepare, host only):
+    specs, four (bits, vals) pairs as huffman_table gives them, in the order DC
+    luma, AC luma, DC chroma, AC chroma (None: an empty table).  Returns a uint8
+    array of hpdct_huffman_blob_bytes() bytes; copy it to the device and pass
+    that tensor as tables= to encode_scan / decode_scan.  A table a DHT segment
+    may not hold is refused with status 1, the message naming table and reason."""
+    lib = load_library()
+    blob = np.zeros(int(lib.hpdct_huffman_blob_bytes()), np.uint8)
+    arr = _huffman_specs(specs)
+    _check(lib.hpdct_huffman_prepare(ctypes.addressof(arr), blob.ctypes.data, blob.size))
+    return blob
+
+
+def huffman_optimal(counts):
+    """(bits, vals) of the optimal table of T.81 K.2 for 256 symbol counts
+    (hpdct_huffman_optimal): no code longer than 16 bits, none all ones."""
+    c = np.ascontiguousarray(np.asarray(counts).astype(np.uint64).ravel())
+    if c.size != 256:
+        raise HpdctError(1, f"256 counts are expected (got {c.size})")
+    out = _HuffmanSpec()
+    _check(load_library().hpdct_huffman_optimal(c.ctypes.data, ctypes.addressof(out)))
+    return _specs_out([out])[0]
+
+
+def scan_bound_tables(blocks: int, intervals: int) -> int:
+    """scan_bound under a caller's tables (hpdct_scan_bound_tables): 417 * blocks + 4 * intervals."""
+    n = int(load_library().hpdct_scan_bound_tables(int(blocks), int(intervals)))
+    if n < 0:
+        raise HpdctError(1, f"no scan bound for {blocks} blocks in {intervals} intervals")
+    return n
+
+
+def _tables_ptr(tables, device):
+    """The device pointer of a table blob (a uint8 tensor of huffman_prepare's bytes), or None."""
+    if tables is None:
+        return None
+    torch = _torch()
+    _device_plane(tables, "tables", device, int(load_library().hpdct_huffman_blob_bytes()), (torch.uint8,))
+    return ctypes.c_void_p(tables.data_ptr())
+
+
 def jpeg_header(height: int, width: int, *, components: int = 3, subsampling: str = "420", q_luma=None,
-                q_chroma=None, restart_interval: int = 0) -> bytes:
+                q_chroma=None, restart_interval: int = 0, tables=None) -> bytes:
     """SOI .. SOS of a baseline file for a scan of encode_scan (hpdct_jpeg_header):
-    height and width are the TRUE frame size; append the scan and FF D9."""
+    height and width are the TRUE frame size; append the scan and FF D9.
+    tables: the four (bits, vals) pairs DHT is to carry (huffman_prepare's
+    specs; hpdct_jpeg_header_tables), None: Annex K's."""
     ql, qc = _host_table(q_luma), _host_table(q_chroma)
-    buf, n = np.zeros(1024, np.uint8), ctypes.c_int64(0)
-    _check(load_library().hpdct_jpeg_header(buf.ctypes.data, buf.size, ctypes.addressof(n), int(height), int(width),
-                                            int(components), _subsampling(subsampling),
-                                            None if ql is None else ql.ctypes.data,
-                                            None if qc is None else qc.ctypes.data, int(restart_interval)))
+    buf, n = np.zeros(2048, np.uint8), ctypes.c_int64(0)
+    args = (buf.ctypes.data, buf.size, ctypes.addressof(n), int(height), int(width), int(components),
+            _subsampling(subsampling), None if ql is None else ql.ctypes.data,
+            None if qc is None else qc.ctypes.data, int(restart_interval))
+    if tables is None:
+        _check(load_library().hpdct_jpeg_header(*args))
+    else:
+        arr = _huffman_specs(tables)
+        _check(load_library().hpdct_jpeg_header_tables(*args, ctypes.addressof(arr)))
     return buf[:n.value].tobytes()
 
 
@@ -852,12 +951,14 @@ def _scan_planes(y, cb, cr, height, width, sub: int, restart_interval: int):
 
 
 def bind_scan(y, cb, cr, scan, info, offsets, workspace, *, height=None, width=None, subsampling: str = "420",
-              restart_interval: int = 0, order: str = "zigzag", capacity=None, stream=None):
+              restart_interval: int = 0, order: str = "zigzag", capacity=None, stream=None, tables=None):
     """Pre-resolved hpdct_encode_scan launch on the given buffers: a
     zero-argument callable like the other bind_* functions (three kernel
     launches, no allocation: it can be captured into a graph).  scan: uint8,
     `capacity` bytes of it (default: all) may be written; info: 16 bytes (two
-    int64); offsets: None or intervals + 1 int64; workspace: uint8."""
+    int64); offsets: None or intervals + 1 int64; workspace: uint8.  tables: a
+    uint8 device tensor holding huffman_prepare's blob (hpdct_encode_scan_tables),
+    None: Annex K's tables."""
     torch = _torch()
     sub, flags = _subsampling(subsampling), _block_flags(order)
     h, w, components, _, intervals, ws = _scan_planes(y, cb, cr, height, width, sub, restart_interval)
@@ -872,9 +973,37 @@ def bind_scan(y, cb, cr, scan, info, offsets, workspace, *, height=None, width=N
     vp = ctypes.c_void_p
     args = (vp(y.data_ptr()), None if cb is None else vp(cb.data_ptr()), None if cr is None else vp(cr.data_ptr()),
             h, w, sub, int(restart_interval), flags, vp(scan.data_ptr()), cap, vp(info.data_ptr()),
-            None if offsets is None else vp(offsets.data_ptr()), vp(workspace.data_ptr()), workspace.numel(),
-            _stream_ptr(stream))
-    return _bound(load_library().hpdct_encode_scan, args)
+            None if offsets is None else vp(offsets.data_ptr()), vp(workspace.data_ptr()), workspace.numel())
+    if tables is not None:
+        return _bound(load_library().hpdct_encode_scan_tables, args + (_tables_ptr(tables, y.device), _stream_ptr(stream)))
+    return _bound(load_library().hpdct_encode_scan, args + (_stream_ptr(stream),))
+
+
+def bind_scan_histogram(y, cb, cr, counts, *, height=None, width=None, subsampling: str = "420",
+                        restart_interval: int = 0, order: str = "zigzag", stream=None):
+    """Pre-resolved hpdct_scan_histogram launch: a zero-argument callable (a
+    memset and one kernel launch, no allocation: it can be captured into a
+    graph).  counts: 4 * 256 int64 on the blocks' device, overwritten."""
+    torch = _torch()
+    sub, flags = _subsampling(subsampling), _block_flags(order)
+    h, w, _, _, _, _ = _scan_planes(y, cb, cr, height, width, sub, restart_interval)
+    _device_plane(counts, "counts", y.device, 1024, (torch.int64,))
+    vp = ctypes.c_void_p
+    args = (vp(y.data_ptr()), None if cb is None else vp(cb.data_ptr()), None if cr is None else vp(cr.data_ptr()),
+            h, w, sub, int(restart_interval), flags, vp(counts.data_ptr()), _stream_ptr(stream))
+    return _bound(load_library().hpdct_scan_histogram, args)
+
+
+def scan_histogram(y, cb=None, cr=None, *, height=None, width=None, subsampling: str = "420",
+                   restart_interval: int = 0, order: str = "zigzag", stream=None):
+    """How often encode_scan emits each symbol of each table for these blocks
+    (hpdct_scan_histogram): a (4, 256) int64 device tensor, rows DC luma, AC
+    luma, DC chroma, AC chroma.  The arguments are encode_scan's."""
+    torch = _torch()
+    counts = torch.empty((4, 256), dtype=torch.int64, device=y.device)
+    bind_scan_histogram(y, cb, cr, counts, height=height, width=width, subsampling=subsampling,
+                        restart_interval=restart_interval, order=order, stream=stream)()
+    return counts
 
 
 def scan_info(info) -> dict:
@@ -884,8 +1013,10 @@ def scan_info(info) -> dict:
 
 
 def encode_scan(y, cb=None, cr=None, *, height=None, width=None, subsampling: str = "420",
-                restart_interval: int = 0, order: str = "zigzag", out=None, stream=None):
+                restart_interval: int = 0, order: str = "zigzag", out=None, stream=None, tables=None):
     """int16 blocks -> the bytes of one baseline Huffman scan, on the device.
+    tables: as bind_scan takes them (a symbol without a code is counted in
+    info["out_of_range"]).
     y alone: grey; y, cb, cr: the arrays of forward_rgb_blocks / forward_rgb_frame
     (height and width: the padded frame).  Returns (scan, info, offsets): the
     uint8 device tensor trimmed to its length, {"bytes", "truncated",
@@ -900,11 +1031,12 @@ def encode_scan(y, cb=None, cr=None, *, height=None, width=None, subsampling: st
     info = torch.empty(2, dtype=torch.int64, device=y.device)
     offsets = torch.empty(intervals + 1, dtype=torch.int64, device=y.device)
     workspace = torch.empty(ws, dtype=torch.uint8, device=y.device)
-    buf = out if out is not None else torch.empty(min(scan_bound(blocks, intervals), 128 * blocks + 4 * intervals),
+    bound = scan_bound(blocks, intervals) if tables is None else scan_bound_tables(blocks, intervals)
+    buf = out if out is not None else torch.empty(min(bound, 128 * blocks + 4 * intervals),
                                                   dtype=torch.uint8, device=y.device)
     while True:
         bind_scan(y, cb, cr, buf, info, offsets, workspace, height=height, width=width, subsampling=subsampling,
-                  restart_interval=restart_interval, order=order, stream=stream)()
+                  restart_interval=restart_interval, order=order, stream=stream, tables=tables)()
         if stream is not None:
             stream.synchronize()
         res = scan_info(info)
@@ -915,14 +1047,20 @@ def encode_scan(y, cb=None, cr=None, *, height=None, width=None, subsampling: st
         buf = torch.empty(res["bytes"], dtype=torch.uint8, device=y.device)
 
 
-def jpeg_encode(image, *, subsampling: str = "420", q_luma=None, q_chroma=None, restart_interval=None) -> bytes:
+def jpeg_encode(image, *, subsampling: str = "420", q_luma=None, q_chroma=None, restart_interval=None,
+                optimize: bool = False) -> bytes:
     """A whole baseline JPEG file from a device frame.  A 2-D uint8 tensor (sizes
     multiples of 8) is a grey frame: forward_blocks under the library table
     (set_quant_table), then encode_scan.  An (H, W, 3) tensor of any size goes
     through forward_rgb_frame with the given tables and subsampling.
     restart_interval None: one MCU row per interval, what the coder is tuned
     for.  A standard decoder inverts with the exact DCT, so the file decodes to
-    an approximation of this library's own inverse."""
+    an approximation of this library's own inverse.
+    optimize: the file carries the optimal Huffman tables of its own symbols
+    instead of Annex K's (scan_histogram, 8 KiB to the host, huffman_optimal for
+    each table in use, huffman_prepare, the blob to the device, then encode_scan
+    and jpeg_header under those tables): a smaller file for one more read of the
+    blocks and one round trip to the host."""
     if image.dim() == 2:
         if q_luma is not None or q_chroma is not None:
             raise HpdctError(2, "a grey frame is coded with the library table (set_quant_table)")
@@ -935,9 +1073,16 @@ def jpeg_encode(image, *, subsampling: str = "420", q_luma=None, q_chroma=None, 
         hp, wp, _, _ = rgb_frame_geometry(h, w, subsampling)
         components, mcu = 3, 16 if subsampling == "420" else 8
     ri = wp // mcu if restart_interval is None else int(restart_interval)
+    specs = blob = None
+    if optimize:
+        counts = scan_histogram(*blocks, height=hp, width=wp, subsampling=subsampling, restart_interval=ri)
+        counts = counts.cpu().numpy()
+        specs = [huffman_optimal(counts[k]) if k < 2 or components == 3 else None for k in range(4)]
+        blob = _torch().from_numpy(huffman_prepare(specs)).to(image.device)
     head = jpeg_header(h, w, components=components, subsampling=subsampling, q_luma=q_luma, q_chroma=q_chroma,
-                       restart_interval=ri)
-    scan, info, _ = encode_scan(*blocks, height=hp, width=wp, subsampling=subsampling, restart_interval=ri)
+                       restart_interval=ri, tables=specs)
+    scan, info, _ = encode_scan(*blocks, height=hp, width=wp, subsampling=subsampling, restart_interval=ri,
+                                tables=blob)
     if info["out_of_range"]:
         raise HpdctError(3, f"{info['out_of_range']} coefficients are beyond baseline JPEG's range "
                             "(DC difference +-2047, AC +-1023): use a coarser quant table")
@@ -973,6 +1118,25 @@ def jpeg_parse(data) -> dict:
             "q_chroma": np.array(lay.q_chroma, np.float32).reshape(8, 8) if lay.components == 3 else None}
 
 
+def jpeg_parse_tables(data) -> dict:
+    """jpeg_parse for a file with any Huffman tables a baseline DHT can carry
+    (hpdct_jpeg_parse_tables): the same dictionary and "tables", the four
+    (bits, vals) pairs the scan's components select (DC luma, AC luma, DC
+    chroma, AC chroma; the chroma pair empty for one component), as
+    huffman_prepare takes them."""
+    buf = np.frombuffer(bytes(data), np.uint8)
+    lay = _JpegLayout()
+    arr = (_HuffmanSpec * 4)()
+    _check(load_library().hpdct_jpeg_parse_tables(buf.ctypes.data if buf.size else ctypes.addressof(lay), buf.size,
+                                                  ctypes.addressof(lay), ctypes.addressof(arr)))
+    names = {v: k for k, v in SUBSAMPLINGS.items()}
+    return {"height": lay.height, "width": lay.width, "components": lay.components, "subsampling": names[lay.sub],
+            "restart_interval": lay.restart_interval, "scan_offset": lay.scan_offset, "scan_bytes": lay.scan_bytes,
+            "q_luma": np.array(lay.q_luma, np.float32).reshape(8, 8),
+            "q_chroma": np.array(lay.q_chroma, np.float32).reshape(8, 8) if lay.components == 3 else None,
+            "tables": _specs_out(arr)}
+
+
 def _decode_geometry(height, width, components, sub: int, restart_interval):
     """(h, w, components, side, nmcu, intervals) of a scan of the padded frame h x w."""
     components, ri = int(components), int(restart_interval)
@@ -997,7 +1161,7 @@ def decode_workspace_bytes(height, width, *, components=1, subsampling="420", re
 
 
 def _bind_decode(split_min_bytes, scan, offsets, y, cb, cr, info, status, workspace, height, width, subsampling,
-                 restart_interval, order, stream):
+                 restart_interval, order, stream, tables=None):
     """bind_decode_scan (split_min_bytes None) and bind_decode_scan_split: the same buffers and checks, the info
     and the workspace the call's own."""
     torch = _torch()
@@ -1035,14 +1199,20 @@ def _bind_decode(split_min_bytes, scan, offsets, y, cb, cr, info, status, worksp
             None if cb is None else vp(cb.data_ptr()), None if cr is None else vp(cr.data_ptr()), h, w, sub,
             int(restart_interval), flags) + ((int(split_min_bytes),) if split else ()) + (
             vp(info.data_ptr()), None if status is None else vp(status.data_ptr()),
-            vp(workspace.data_ptr()), workspace.numel(), _stream_ptr(stream))
+            vp(workspace.data_ptr()), workspace.numel())
     lib = load_library()
-    return _bound(lib.hpdct_decode_scan_split if split else lib.hpdct_decode_scan, args)
+    if tables is not None:
+        return _bound(lib.hpdct_decode_scan_split_tables if split else lib.hpdct_decode_scan_tables,
+                      args + (_tables_ptr(tables, y.device), _stream_ptr(stream)))
+    return _bound(lib.hpdct_decode_scan_split if split else lib.hpdct_decode_scan, args + (_stream_ptr(stream),))
 
 
 def bind_decode_scan(scan, offsets, y, cb, cr, info, status, workspace, *, height=None, width=None,
-                     subsampling: str = "420", restart_interval: int = 0, order: str = "zigzag", stream=None):
-    """Pre-resolved hpdct_decode_scan launch on the given buffers: a
+                     subsampling: str = "420", restart_interval: int = 0, order: str = "zigzag", stream=None,
+                     tables=None):
+    """Pre-resolved hpdct_decode_scan launch on the given buffers (tables: a
+    uint8 device tensor holding huffman_prepare's blob, hpdct_decode_scan_tables;
+    None: Annex K's): a
     zero-argument callable like the other bind_* functions (two kernel launches
     with offsets, four without, no allocation: it can be captured into a graph).
     scan: uint8, all of it is the scan; offsets: None (the markers are located)
@@ -1050,7 +1220,7 @@ def bind_decode_scan(scan, offsets, y, cb, cr, info, status, workspace, *, heigh
     grey); info: 16 bytes (two int64); status: None or `intervals` int64;
     workspace: uint8."""
     return _bind_decode(None, scan, offsets, y, cb, cr, info, status, workspace, height, width, subsampling,
-                        restart_interval, order, stream)
+                        restart_interval, order, stream, tables)
 
 
 def decode_split_geometry():
@@ -1074,15 +1244,16 @@ def decode_split_workspace_bytes(height, width, *, components=1, subsampling="42
 
 def bind_decode_scan_split(scan, offsets, y, cb, cr, info, status, workspace, *, height=None, width=None,
                            subsampling: str = "420", restart_interval: int = 0, order: str = "zigzag",
-                           split_min_bytes: int = 0, stream=None):
+                           split_min_bytes: int = 0, stream=None, tables=None):
     """Pre-resolved hpdct_decode_scan_split launch: bind_decode_scan's buffers,
     but info of 32 bytes (four int64) and a workspace of
     decode_split_workspace_bytes(...) bytes.  split_min_bytes: intervals of at
     least this many bytes are split (0: the library's choice; 1: all but empty
     ones).  Eleven launches with offsets, thirteen without, none of which waits
-    for the host: it can be captured into a graph."""
+    for the host: it can be captured into a graph.  tables: as bind_decode_scan
+    takes them (hpdct_decode_scan_split_tables)."""
     return _bind_decode(int(split_min_bytes), scan, offsets, y, cb, cr, info, status, workspace, height, width,
-                        subsampling, restart_interval, order, stream)
+                        subsampling, restart_interval, order, stream, tables)
 
 
 def decode_split_info(info) -> dict:
@@ -1101,7 +1272,7 @@ def decode_info(info) -> dict:
 
 def decode_scan(scan, *, height, width, components: int = 1, subsampling: str = "420", restart_interval: int = 0,
                 offsets=None, order: str = "zigzag", out=None, stream=None, method: str = "serial",
-                split_min_bytes: int = 0):
+                split_min_bytes: int = 0, tables=None):
     """The bytes of one baseline Huffman scan -> int16 blocks, on the device: the
     inverse of encode_scan.  scan: a uint8 device tensor, all of it the scan;
     height and width: the padded frame; offsets: encode_scan's table, or None
@@ -1115,7 +1286,9 @@ def decode_scan(scan, *, height, width, components: int = 1, subsampling: str = 
     (hpdct_decode_scan, one lane per restart interval) or "split"
     (hpdct_decode_scan_split, parallel inside an interval of at least
     split_min_bytes bytes as well: the same blocks and status, and info has the
-    four counters of decode_split_info besides).  Synchronises to read info."""
+    four counters of decode_split_info besides).  tables: a uint8 device tensor
+    holding huffman_prepare's blob, the tables the scan was coded with (None:
+    Annex K's).  Synchronises to read info."""
     torch = _torch()
     sub = _subsampling(subsampling)
     if method not in ("serial", "split"):
@@ -1138,7 +1311,7 @@ def decode_scan(scan, *, height, width, components: int = 1, subsampling: str = 
         scan_bytes=scan.numel())
     workspace = torch.empty(ws, dtype=torch.uint8, device=dev)
     _bind_decode(int(split_min_bytes) if split else None, scan, offsets, y, cb, cr, info, status, workspace, h, w,
-                 subsampling, restart_interval, order, stream)()
+                 subsampling, restart_interval, order, stream, tables)()
     if stream is not None:
         stream.synchronize()
     return tuple(out), (decode_split_info if split else decode_info)(info), status
@@ -1157,13 +1330,18 @@ def jpeg_decode(data, *, device=None, method: str = "auto"):
     (bad_intervals != 0) raises.  method: "serial" or "split" as decode_scan
     takes them, or "auto": the split call when the scan has SPLIT_MIN_BYTES
     bytes per restart interval or more (a file without restart markers is one
-    interval), the serial call below that."""
+    interval), the serial call below that.  A file with Huffman tables of its
+    own (jpeg_parse_tables; an optimised file) is decoded under them."""
     torch = _torch()
     data = bytes(data)
     if method not in ("auto", "serial", "split"):
         raise ValueError(f"method must be 'auto', 'serial' or 'split' (got {method!r})")
-    lay = jpeg_parse(data)
+    lay = jpeg_parse_tables(data)
     dev = torch.device(device if device is not None else "cuda")
+    annex = all(sp is None or (np.array_equal(sp[0], t[0]) and np.array_equal(sp[1], t[1]))
+                for sp, t in zip([huffman_table(k) if k < 2 or lay["components"] == 3 else None for k in range(4)],
+                                 lay["tables"]))
+    tables = None if annex else torch.from_numpy(huffman_prepare(lay["tables"])).to(dev)
     h, w, comps, sub = lay["height"], lay["width"], lay["components"], lay["subsampling"]
     if comps == 1:
         if not np.array_equal(lay["q_luma"], get_quant_table().reshape(8, 8)):
@@ -1178,7 +1356,7 @@ def jpeg_decode(data, *, device=None, method: str = "auto"):
         intervals = _decode_geometry(hp_, wp_, comps, _subsampling(sub), lay["restart_interval"])[5]
         method = "split" if lay["scan_bytes"] >= SPLIT_MIN_BYTES * intervals else "serial"
     blocks, info, status = decode_scan(scan, height=hp_, width=wp_, components=comps, subsampling=sub,
-                                       restart_interval=lay["restart_interval"], method=method)
+                                       restart_interval=lay["restart_interval"], method=method, tables=tables)
     if info["bad_intervals"]:
         first = int(torch.nonzero(status)[0])
         code = int(status[first]) & 255

@@ -657,6 +657,105 @@ typedef struct hpdct_jpeg_layout {
 } hpdct_jpeg_layout;
 hpdct_status hpdct_jpeg_parse(const uint8_t* h_file, int64_t bytes, hpdct_jpeg_layout* out);
 
+/* Huffman tables from the caller: the entropy coder and the
+ * entropy decoders under any four tables a baseline DHT can carry, the
+ * statistics of a frame's symbols, and the optimal tables for them.
+ *
+ * A table as a DHT segment holds it: bits[l-1] = the number of codes of length
+ * l, vals[0 .. nvals) the symbols in order of increasing code length.  Kinds as
+ * hpdct_huffman_table: 0 DC luma, 1 AC luma, 2 DC chroma, 3 AC chroma.  An
+ * empty table (nvals == 0) is legal and codes nothing.
+ *
+ * hpdct_huffman_prepare (host only, no allocation, no process-wide state)
+ * judges four specs and writes one POD blob of hpdct_huffman_blob_bytes()
+ * bytes into h_blob: the coder's (length << 16) | code entries per symbol, then
+ * the decoder's 8-bit lookup, maxcode, valoff and vals (256 symbols a table).
+ * The caller copies the blob to device memory (16-byte aligned) and passes that
+ * pointer as d_tables below.  HPDCT_ERROR_INVALID_VALUE, the message naming the
+ * table and the reason: nvals is not the sum of bits or is above 256; the code
+ * is over-subscribed (Kraft sum above 1 with the lengths assigned canonically);
+ * a symbol appears twice; a DC symbol is above 15; a null pointer; capacity
+ * below the blob's size.  The blob is the caller's data: the kernels mask every
+ * index they form from it and clamp its code lengths to 16, so they stay
+ * memory-safe whatever it holds, but only a blob prepare wrote gives a JPEG scan.
+ *
+ * hpdct_huffman_optimal (host only): the table of T.81 K.2 (figures K.1 - K.4)
+ * for the symbol counts counts[0 .. 256): a pseudo-symbol 256 of count 1, so
+ * that no symbol gets the all-ones code; the two smallest non-zero counts are
+ * merged until one is left, on ties the larger symbol index for the first and
+ * for the second choice; the lengths above 16 are adjusted as figure K.3 does;
+ * the pseudo-symbol leaves the longest length; vals by length, then by symbol
+ * value.  All-zero counts give nvals == 0, one non-zero count one code of
+ * length 1.  A count above 2^54 is refused with HPDCT_ERROR_INVALID_VALUE (the
+ * sum of all of them must stay below 2^63); a frame's counts stay below 2^38.
+ *
+ * hpdct_scan_histogram (device, one memset and one launch, no allocation, can
+ * be captured into a graph): d_counts[kind * 256 + s], 4 * 256 uint64, 16-byte
+ * aligned, overwritten, = exactly the number of times hpdct_encode_scan emits
+ * symbol s of table kind for the same arguments: a DC category of the
+ * difference hpdct_encode_scan codes (0 at an interval's start), a ZRL per 16
+ * zeros, an EOB unless coefficient 63 is non-zero, the categories clamped to
+ * 11 (DC) and 10 (AC) as the coder clamps them.  The pass is parallel over
+ * blocks and does not depend on restart_interval.  Checks and errors:
+ * hpdct_encode_scan's for the blocks, the geometry and the flags. */
+typedef struct hpdct_huffman_spec {
+    uint8_t bits[16];
+    uint8_t vals[256];
+    int32_t nvals;
+} hpdct_huffman_spec;
+int64_t hpdct_huffman_blob_bytes(void);
+hpdct_status hpdct_huffman_prepare(const hpdct_huffman_spec specs[4], void* h_blob, int64_t capacity);
+hpdct_status hpdct_huffman_optimal(const uint64_t counts[256], hpdct_huffman_spec* out);
+hpdct_status hpdct_scan_histogram(const int16_t* d_y, const int16_t* d_cb, const int16_t* d_cr, int64_t height,
+                                  int64_t width, hpdct_subsampling sub, int64_t restart_interval, unsigned flags,
+                                  uint64_t* d_counts, void* stream);
+/* hpdct_encode_scan, hpdct_decode_scan and hpdct_decode_scan_split with a table blob: d_tables NULL
+ * means Annex K, bit for bit the calls without it.  Every documented contract
+ * of those calls carries over.  With a 16-bit DC code a block reaches 27 + 63 *
+ * 26 = 1665 bits, so the bound is hpdct_scan_bound_tables(blocks, intervals) =
+ * 417 * blocks + 4 * intervals.  A symbol the caller's table has no code for is
+ * counted in info.out_of_range; the bytes are then unspecified, the call still
+ * memory-safe and info.bytes within the bound.  The decoder takes DC symbols up
+ * to 15 (the int16 check of the DC stands); a code of an empty or incomplete
+ * table ends the interval with status code 4 (CODE). */
+int64_t hpdct_scan_bound_tables(int64_t blocks, int64_t intervals); /* host: worst-case bytes */
+hpdct_status hpdct_encode_scan_tables(const int16_t* d_y, const int16_t* d_cb, const int16_t* d_cr, int64_t height,
+                                      int64_t width, hpdct_subsampling sub, int64_t restart_interval, unsigned flags,
+                                      uint8_t* d_scan, int64_t capacity, hpdct_scan_info* d_info,
+                                      uint64_t* d_interval_offsets /* or NULL */, void* d_workspace,
+                                      int64_t workspace_bytes, const void* d_tables /* or NULL */, void* stream);
+hpdct_status hpdct_decode_scan_tables(const uint8_t* d_scan, int64_t bytes,
+                                      const uint64_t* d_interval_offsets /* or NULL */, int16_t* d_y, int16_t* d_cb,
+                                      int16_t* d_cr, int64_t height, int64_t width, hpdct_subsampling sub,
+                                      int64_t restart_interval, unsigned flags, hpdct_decode_info* d_info,
+                                      uint64_t* d_interval_status /* or NULL */, void* d_workspace,
+                                      int64_t workspace_bytes, const void* d_tables /* or NULL */, void* stream);
+/* hpdct_decode_scan_split under the caller's tables: bit for bit
+ * hpdct_decode_scan_tables in blocks, status and the info's first three words. */
+hpdct_status hpdct_decode_scan_split_tables(const uint8_t* d_scan, int64_t bytes,
+                                            const uint64_t* d_interval_offsets /* or NULL */, int16_t* d_y,
+                                            int16_t* d_cb, int16_t* d_cr, int64_t height, int64_t width,
+                                            hpdct_subsampling sub, int64_t restart_interval, unsigned flags,
+                                            int64_t split_min_bytes, hpdct_decode_split_info* d_info,
+                                            uint64_t* d_interval_status /* or NULL */, void* d_workspace,
+                                            int64_t workspace_bytes, const void* d_tables /* or NULL */,
+                                            void* stream);
+/* hpdct_jpeg_header with the tables to write into DHT (kinds 0, 1 alone for
+ * one component): specs NULL means Annex K, byte for byte hpdct_jpeg_header;
+ * specs that hpdct_huffman_prepare refuses are refused alike.
+ * hpdct_jpeg_parse_tables: the walk and the refusals of hpdct_jpeg_parse,
+ * except that any DHT hpdct_huffman_prepare accepts is accepted and returned
+ * in specs[4]: Y selects kinds 0 / 1; Cb and Cr must select tables of equal
+ * contents (kinds 2 / 3; one component: both empty), else
+ * HPDCT_ERROR_UNSUPPORTED "Cb and Cr on different Huffman tables"; a table that
+ * fails the validation gives HPDCT_ERROR_INVALID_VALUE with prepare's reason. */
+hpdct_status hpdct_jpeg_header_tables(uint8_t* h_out, int64_t capacity, int64_t* bytes, int64_t height,
+                                      int64_t width, int components, hpdct_subsampling sub, const float* q_luma64,
+                                      const float* q_chroma64, int64_t restart_interval,
+                                      const hpdct_huffman_spec specs[4] /* or NULL */);
+hpdct_status hpdct_jpeg_parse_tables(const uint8_t* h_file, int64_t bytes, hpdct_jpeg_layout* out,
+                                     hpdct_huffman_spec specs[4]);
+
 /* Work mapping of the kernels (new; the reference has one fixed decomposition
  * per program).  Output is bit-identical in every mapping; only speed differs.
  *   AUTO   per frame: eight lanes per 8x8 tile ("octet") for frames below
