@@ -1,7 +1,7 @@
 // hpdct_huffman.hpp -- Huffman tables as the caller's data: the
 // judgement of a DHT's contents, the blob the *_tables calls read
 // (unscan::HuffBlob), and the optimal table of T.81 K.2.  Plain C++, host only,
-// no allocation: hpdct_api.cpp and tests/tools/asan_huffman_check.cpp include it.
+// no allocation: hpdct_api_jpeg.cpp and tests/tools/asan_huffman_check.cpp include it.
 #pragma once
 
 #include <stdint.h>
@@ -39,44 +39,21 @@ inline const char* defect(const hpdct_huffman_spec& s, int kind) {
     return nullptr;
 }
 
-inline hpdct_huffman_spec annex_k(int kind) {
-    const scan::HuffSpec& k = scan::spec_of(kind);
-    hpdct_huffman_spec s;
-    memset(&s, 0, sizeof(s));
-    memcpy(s.bits, k.bits, 16);
-    memcpy(s.vals, k.vals, static_cast<size_t>(k.nvals));
-    s.nvals = k.nvals;
-    return s;
-}
+// Annex K's table `kind`, the definition of hpdct_scan.hpp (its unused vals are 0)
+inline hpdct_huffman_spec annex_k(int kind) { return scan::spec_of(kind); }
 inline bool same_table(const hpdct_huffman_spec& a, const hpdct_huffman_spec& b) {
     return a.nvals == b.nvals && memcmp(a.bits, b.bits, 16) == 0 &&
            memcmp(a.vals, b.vals, static_cast<size_t>(a.nvals < 0 ? 0 : a.nvals)) == 0;
 }
 
-// The blob of four specs that passed defect(): as scan::fill_codes and
-// unscan::fill_decode fill the Annex K tables.  A symbol without a code has the
-// entry 0 (length 0); a lookup slot no code of 8 bits or fewer covers is 0.
+// The blob of four specs that passed defect(), by the builders that fill the Annex K constants: scan::fill_codes
+// and unscan::fill_decode.  A symbol without a code has the entry 0 (length 0); a lookup slot no code of 8 bits
+// or fewer covers is 0.
 inline void fill_blob(const hpdct_huffman_spec specs[4], unscan::HuffBlob& b) {
     memset(&b, 0, sizeof(b));
     for (int kind = 0; kind < 4; ++kind) {
-        const hpdct_huffman_spec& s = specs[kind];
-        uint32_t* e = (kind & 1) ? b.code.ac[kind >> 1] : b.code.dc[kind >> 1];
-        unscan::DecodeTablesWide& t = b.dec;
-        int code = 0, k = 0;
-        for (int l = 0; l < 18; ++l) t.maxcode[kind][l] = -1, t.valoff[kind][l] = 0;
-        for (int len = 1; len <= 16; ++len) {
-            t.valoff[kind][len] = k - code;
-            for (int i = 0; i < s.bits[len - 1]; ++i) {
-                e[s.vals[k]] = (static_cast<uint32_t>(len) << 16) | static_cast<uint32_t>(code);
-                if (len <= 8)
-                    for (int f = 0; f < (1 << (8 - len)); ++f)
-                        t.look[kind][(code << (8 - len)) | f] = static_cast<uint16_t>((len << 8) | s.vals[k]);
-                t.vals[kind][k] = s.vals[k];
-                ++k, ++code;
-            }
-            if (s.bits[len - 1] != 0) t.maxcode[kind][len] = code - 1;
-            code <<= 1;
-        }
+        scan::fill_codes(specs[kind], (kind & 1) ? b.code.ac[kind >> 1] : b.code.dc[kind >> 1]);
+        unscan::fill_decode(specs[kind], b.dec, kind);
     }
 }
 

@@ -6,6 +6,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <type_traits>
+
 namespace hpdct {
 
 constexpr uint32_t kBlockThreads = 256;  // 4 wave64 per workgroup
@@ -93,6 +95,17 @@ enum : unsigned {
 };
 constexpr uint32_t unscan_lanes_of(unsigned var) {
     return (var & kUnscanLanes16) ? 16u : (var & kUnscanLanes4) ? 4u : (var & kUnscanLanes1) ? 1u : 64u;
+}
+// Runtime -> compile time, as policy::with_bit: f gets var's kUnscanLanes* bit (0: all 64 lanes) as a
+// std::integral_constant.  The serial decoder and the split decoder's serial launch pick their kernel through it.
+template <typename F>
+auto with_lanes(unsigned var, F&& f) {
+    switch (unscan_lanes_of(var)) {
+        case 1u: return f(std::integral_constant<unsigned, kUnscanLanes1>{});
+        case 4u: return f(std::integral_constant<unsigned, kUnscanLanes4>{});
+        case 16u: return f(std::integral_constant<unsigned, kUnscanLanes16>{});
+        default: return f(std::integral_constant<unsigned, 0u>{});
+    }
 }
 // the split entropy decoder's kernels (hpdct_unscan_split.hpp): which one, in bits 29..31; its serial kernel also
 // reads the kUnscanLanes* bits, its write and serial kernels kScanNatural

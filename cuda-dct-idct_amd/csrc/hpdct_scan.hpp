@@ -1,8 +1,10 @@
 // hpdct_scan.hpp -- the baseline-JPEG entropy coder (hpdct_encode_scan): int16
 // coefficient blocks -> the Huffman-coded bytes of one interleaved scan (ITU-T
 // T.81 baseline, the typical tables of Annex K.3).  The host part (the tables,
-// the scan's geometry, the bound) is plain C++: hpdct_api.cpp includes it under
-// g++ too.  The kernels are compiled by hpdct_scan.hip only (HPDCT_SCAN_KERNELS).
+// the scan's geometry, the bound) is plain C++: hpdct_api_jpeg.cpp includes it
+// under g++ too.  The kernels are compiled by hpdct_scan.hip only (HPDCT_SCAN_KERNELS).
+// fill_codes is the one builder of the coder's entries, for Annex K's constants
+// and a caller's blob alike; launch_scan is the one launch path for both.
 //
 // Three launches, one chain:
 //   1. measure  one wave per restart interval, 64 blocks of the interval (in
@@ -33,20 +35,20 @@
 #include "hpdct_zigzag.h"
 
 namespace hpdct {
+namespace unscan {
+struct HuffBlob;  // hpdct_unscan.hpp
+}
 namespace scan {
 
 // ITU-T T.81 Annex K.3, tables K.3 - K.6: bits[l-1] = number of codes of length
-// l, vals = the symbols in order of increasing code length.
-struct HuffSpec {
-    uint8_t bits[16];
-    int nvals;
-    uint8_t vals[162];
-};
-constexpr HuffSpec kDcLuma = {{0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, 12, {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11}};
-constexpr HuffSpec kDcChroma = {{0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}, 12, {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11}};
-constexpr HuffSpec kAcLuma = {
+// l, vals = the symbols in order of increasing code length.  The one definition: hpdct_huffman_table, the
+// device constants below and in hpdct_unscan.hpp, and huff::annex_k (hpdct_huffman.hpp) all read it.
+constexpr hpdct_huffman_spec kDcLuma = {
+    {0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0}, {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11}, 12};
+constexpr hpdct_huffman_spec kDcChroma = {
+    {0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0}, {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11}, 12};
+constexpr hpdct_huffman_spec kAcLuma = {
     {0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d},
-    162,
     {0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71,
      0x14, 0x32, 0x81, 0x91, 0xa1, 0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72,
      0x82, 0x09, 0x0a, 0x16, 0x17, 0x18, 0x19, 0x1a, 0x25, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37,
@@ -55,10 +57,10 @@ constexpr HuffSpec kAcLuma = {
      0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a, 0xa2, 0xa3,
      0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3,
      0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2,
-     0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa}};
-constexpr HuffSpec kAcChroma = {
+     0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa},
+    162};
+constexpr hpdct_huffman_spec kAcChroma = {
     {0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77},
-    162,
     {0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22,
      0x32, 0x81, 0x08, 0x14, 0x42, 0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1,
      0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25, 0xf1, 0x17, 0x18, 0x19, 0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36,
@@ -67,9 +69,10 @@ constexpr HuffSpec kAcChroma = {
      0x82, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99, 0x9a,
      0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba,
      0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda,
-     0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa}};
+     0xe2, 0xe3, 0xe4, 0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa},
+    162};
 // kind: 0 DC luma, 1 AC luma, 2 DC chroma, 3 AC chroma (hpdct_huffman_table)
-constexpr const HuffSpec& spec_of(int kind) {
+constexpr const hpdct_huffman_spec& spec_of(int kind) {
     return kind == 0 ? kDcLuma : kind == 1 ? kAcLuma : kind == 2 ? kDcChroma : kAcChroma;
 }
 
@@ -81,7 +84,9 @@ struct CodeTables {
     uint32_t dc[2][16];
 };
 constexpr int kCodeTableWords = 2 * 256 + 2 * 16;
-constexpr void fill_codes(const HuffSpec& s, uint32_t* e) {
+// the entries of one table, for Annex K's specs at compile time and a caller's at run time (huff::fill_blob);
+// a symbol without a code keeps the entry it had (0: length 0)
+constexpr void fill_codes(const hpdct_huffman_spec& s, uint32_t* e) {
     uint32_t code = 0;
     int k = 0;
     for (uint32_t len = 1; len <= 16; ++len) {
@@ -98,7 +103,7 @@ constexpr CodeTables make_code_tables() {
     return t;
 }
 // the longest code of a table
-constexpr int longest_code(const HuffSpec& s) {
+constexpr int longest_code(const hpdct_huffman_spec& s) {
     int l = 0;
     for (int i = 0; i < 16; ++i)
         if (s.bits[i] != 0) l = i + 1;
@@ -169,15 +174,12 @@ static_assert(kPrivStrideT % 2u == 1u && kPrivStrideT > (kMaxBlockBitsT + 31) / 
 // The three launches on s, as policy::scan_code / scan_offsets choose them
 // (hpdct_scan.hip).  cb == cr == nullptr with g.bpm == 1; workspace holds
 // scan::workspace_bytes(g.intervals) bytes, 16-byte aligned; user_offs
-// (g.intervals + 1 entries) may be nullptr.  The caller checked everything.
+// (g.intervals + 1 entries) may be nullptr.  blob nullptr: Annex K's kernels;
+// else the caller's tables, a HuffBlob (hpdct_unscan.hpp) in device memory, of
+// which the coder reads the leading scan::CodeTables.  The caller checked everything.
 hipError_t launch_scan(const int16_t* y, const int16_t* cb, const int16_t* cr, const scan::ScanGrid& g, bool natural,
                        uint8_t* out, uint64_t capacity, hpdct_scan_info* info, uint64_t* user_offs, void* workspace,
-                       hipStream_t s);
-// the same under the caller's tables: d_tables a HuffBlob (hpdct_unscan.hpp) in
-// device memory, of which the coder reads the leading scan::CodeTables
-hipError_t launch_scan_tables(const int16_t* y, const int16_t* cb, const int16_t* cr, const scan::ScanGrid& g,
-                              bool natural, uint8_t* out, uint64_t capacity, hpdct_scan_info* info,
-                              uint64_t* user_offs, void* workspace, const void* d_tables, hipStream_t s);
+                       const unscan::HuffBlob* blob, hipStream_t s);
 // hpdct_scan_histogram (hpdct_scan_hist.hpp): a memset of counts (4 * 256 uint64) and one launch
 hipError_t launch_scan_hist(const int16_t* y, const int16_t* cb, const int16_t* cr, const scan::ScanGrid& g,
                             bool natural, uint64_t* counts, hipStream_t s);

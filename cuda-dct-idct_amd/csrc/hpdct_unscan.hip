@@ -1,32 +1,10 @@
-// hpdct_unscan.hip -- the entropy decoder's launches (hpdct_unscan.hpp).
+// hpdct_unscan.hip -- the entropy decoder's launches (hpdct_unscan.hpp).  The kernels are named here in the order
+// the code object holds them (profiles/r14/README.md): all of Annex K's, then all that read the caller's tables.
 #define HPDCT_UNSCAN_KERNELS
 #include "hpdct_unscan.hpp"
 #include "hpdct_launch.hpp"
 
 namespace hpdct {
-
-namespace {
-template <unsigned kLaneBit>
-hipError_t launch_unscan_decode(const policy::Choice& c, hipStream_t s, const uint8_t* scan, uint64_t bytes,
-                                const uint64_t* offs, const uint64_t* mpos, int16_t* y, int16_t* cb, int16_t* cr,
-                                const scan::ScanGrid& g, hpdct_decode_info* info, uint64_t* status) {
-    return policy::with_bit<kScanNatural, true>(c.var, [&](auto kN) {
-        constexpr unsigned kV = with_block<64>(decltype(kN)::value | kLaneBit);
-        return launch_choice<kV, unscan_decode_kernel<kV>>(c, s, scan, bytes, offs, mpos, y, cb, cr, g, info, status);
-    });
-}
-template <unsigned kLaneBit>
-hipError_t launch_unscan_decode_tables(const policy::Choice& c, hipStream_t s, const uint8_t* scan, uint64_t bytes,
-                                       const uint64_t* offs, const uint64_t* mpos, int16_t* y, int16_t* cb,
-                                       int16_t* cr, const scan::ScanGrid& g, hpdct_decode_info* info,
-                                       uint64_t* status, const unscan::HuffBlob* blob) {
-    return policy::with_bit<kScanNatural, true>(c.var, [&](auto kN) {
-        constexpr unsigned kV = with_block<64>(decltype(kN)::value | kLaneBit | kScanTables);
-        return launch_choice<kV, unscan_decode_tables_kernel<kV>>(c, s, scan, bytes, offs, mpos, y, cb, cr, g, info,
-                                                                  status, blob);
-    });
-}
-}  // namespace
 
 hipError_t launch_unscan_locate(const uint8_t* scan, uint64_t bytes, const uint64_t* offs, const scan::ScanGrid& g,
                                 hpdct_decode_info* info, void* workspace, hipStream_t s) {
@@ -51,44 +29,28 @@ hipError_t launch_unscan_locate(const uint8_t* scan, uint64_t bytes, const uint6
 
 hipError_t launch_unscan(const uint8_t* scan, uint64_t bytes, const uint64_t* offs, int16_t* y, int16_t* cb,
                          int16_t* cr, const scan::ScanGrid& g, bool natural, hpdct_decode_info* info, uint64_t* status,
-                         void* workspace, hipStream_t s) {
+                         void* workspace, const unscan::HuffBlob* blob, hipStream_t s) {
     if (hipError_t e = launch_unscan_locate(scan, bytes, offs, g, info, workspace, s)) return e;
     const uint64_t* mpos = static_cast<const uint64_t*>(workspace);
     policy::UnscanCall pc;
-    pc.intervals = g.intervals, pc.natural = natural;
+    pc.intervals = g.intervals, pc.natural = natural, pc.tables = blob != nullptr;
     const policy::Choice c = policy::unscan_decode(pc);
-    const uint64_t* cmpos = mpos;
-    switch (unscan_lanes_of(c.var)) {
-        case 1u: return launch_unscan_decode<kUnscanLanes1>(c, s, scan, bytes, offs, cmpos, y, cb, cr, g, info, status);
-        case 4u: return launch_unscan_decode<kUnscanLanes4>(c, s, scan, bytes, offs, cmpos, y, cb, cr, g, info, status);
-        case 16u:
-            return launch_unscan_decode<kUnscanLanes16>(c, s, scan, bytes, offs, cmpos, y, cb, cr, g, info, status);
-        default: return launch_unscan_decode<0u>(c, s, scan, bytes, offs, cmpos, y, cb, cr, g, info, status);
-    }
-}
-
-hipError_t launch_unscan_tables(const uint8_t* scan, uint64_t bytes, const uint64_t* offs, int16_t* y, int16_t* cb,
-                                int16_t* cr, const scan::ScanGrid& g, bool natural, hpdct_decode_info* info,
-                                uint64_t* status, void* workspace, const void* d_tables, hipStream_t s) {
-    if (hipError_t e = launch_unscan_locate(scan, bytes, offs, g, info, workspace, s)) return e;
-    const uint64_t* mpos = static_cast<const uint64_t*>(workspace);
-    const unscan::HuffBlob* blob = static_cast<const unscan::HuffBlob*>(d_tables);
-    policy::UnscanCall pc;
-    pc.intervals = g.intervals, pc.natural = natural, pc.tables = true;
-    const policy::Choice c = policy::unscan_decode(pc);
-    switch (unscan_lanes_of(c.var)) {
-        case 1u:
-            return launch_unscan_decode_tables<kUnscanLanes1>(c, s, scan, bytes, offs, mpos, y, cb, cr, g, info, status,
-                                                              blob);
-        case 4u:
-            return launch_unscan_decode_tables<kUnscanLanes4>(c, s, scan, bytes, offs, mpos, y, cb, cr, g, info, status,
-                                                              blob);
-        case 16u:
-            return launch_unscan_decode_tables<kUnscanLanes16>(c, s, scan, bytes, offs, mpos, y, cb, cr, g, info,
-                                                               status, blob);
-        default:
-            return launch_unscan_decode_tables<0u>(c, s, scan, bytes, offs, mpos, y, cb, cr, g, info, status, blob);
-    }
+    // kT: 0 for Annex K's kernels, kScanTables for those that read the caller's blob
+    auto decode = [&](auto kT) {
+        return with_lanes(c.var, [&](auto kL) {
+            return policy::with_bit<kScanNatural, true>(c.var, [&](auto kN) {
+                constexpr unsigned kV = with_block<64>(decltype(kN)::value | decltype(kL)::value | decltype(kT)::value);
+                if constexpr (decltype(kT)::value != 0u)
+                    return launch_choice<kV, unscan_decode_tables_kernel<kV>>(c, s, scan, bytes, offs, mpos, y, cb, cr,
+                                                                              g, info, status, blob);
+                else
+                    return launch_choice<kV, unscan_decode_kernel<kV>>(c, s, scan, bytes, offs, mpos, y, cb, cr, g,
+                                                                       info, status);
+            });
+        });
+    };
+    if (!blob) return decode(std::integral_constant<unsigned, 0u>{});
+    return decode(std::integral_constant<unsigned, kScanTables>{});
 }
 
 }  // namespace hpdct

@@ -24,6 +24,13 @@
 //              within a wave by ballot and popcount; the numbering is checked;
 //   4. decode  one lane per interval.
 // No workgroup waits on another; the only atomics are integer sums.
+//
+// unscan::fill_decode is the one builder of a decode table, for Annex K's
+// constants (make_decode_tables, at compile time) and a caller's blob
+// (huff::fill_blob, hpdct_huffman.hpp) alike; launch_unscan is the one launch
+// path for both.  The decode kernel keeps an instantiation for each: the
+// caller's tables are untrusted and cost masks in the walk, and what those
+// would cost the Annex K path is unmeasured.
 #pragma once
 
 #include <stdint.h>
@@ -61,7 +68,11 @@ struct DecodeTables {
 };
 constexpr int kTableWords = static_cast<int>(sizeof(DecodeTables) / 4u);
 static_assert(sizeof(DecodeTables) == 4u * kTableWords && sizeof(DecodeTables) == 3280u, "tables are packed");
-constexpr void fill_decode(const scan::HuffSpec& s, DecodeTables& t, int kind) {
+// table `kind` of Tab (DecodeTables, or DecodeTablesWide below: they differ in the width of vals), for Annex K's
+// specs at compile time and a caller's at run time (huff::fill_blob); a lookup slot no code of 8 bits or fewer
+// covers keeps what it had (0)
+template <class Tab>
+constexpr void fill_decode(const hpdct_huffman_spec& s, Tab& t, int kind) {
     int code = 0, k = 0;
     for (int l = 0; l < 18; ++l) t.maxcode[kind][l] = -1, t.valoff[kind][l] = 0;
     for (int len = 1; len <= 16; ++len) {
@@ -102,6 +113,16 @@ struct HuffBlob {
 static_assert(sizeof(HuffBlob) == 5824u && sizeof(HuffBlob) % 16u == 0u, "the blob is packed");
 template <class Tab>
 constexpr bool kUntrusted = std::is_same_v<Tab, DecodeTablesWide>;
+
+// zigzag::kOrder as the device constant the decoders stage into LDS (kUnscanOrder, kUnsplitOrder)
+struct ZigzagOrder {
+    uint8_t v[64];
+};
+constexpr ZigzagOrder make_zigzag_order() {
+    ZigzagOrder o{};
+    for (int n = 0; n < 64; ++n) o.v[n] = zigzag::kOrder[n];
+    return o;
+}
 
 // The workspace: the byte position of the j-th marker for j < intervals
 // (uint64), then a uint64 per 4096-byte chunk of the scan (its marker count,
@@ -362,14 +383,11 @@ HPDCT_HD uint64_t walk_interval(const uint8_t* scan, uint64_t lo, uint64_t hi, u
 // The launches on s, as policy::unscan_* choose them (hpdct_unscan.hip).  offs
 // (g.intervals + 1 entries) may be nullptr: the markers are located then, and
 // workspace holds unscan::workspace_bytes(g.intervals, bytes) bytes, 16-byte
-// aligned.  status (g.intervals entries) may be nullptr.  The caller checked everything.
+// aligned.  status (g.intervals entries) may be nullptr.  blob nullptr: Annex K's
+// kernels; else the caller's tables, a HuffBlob in device memory.  The caller checked everything.
 hipError_t launch_unscan(const uint8_t* scan, uint64_t bytes, const uint64_t* offs, int16_t* y, int16_t* cb,
                          int16_t* cr, const scan::ScanGrid& g, bool natural, hpdct_decode_info* info, uint64_t* status,
-                         void* workspace, hipStream_t s);
-// the same under the caller's tables: d_tables a HuffBlob in device memory
-hipError_t launch_unscan_tables(const uint8_t* scan, uint64_t bytes, const uint64_t* offs, int16_t* y, int16_t* cb,
-                                int16_t* cr, const scan::ScanGrid& g, bool natural, hpdct_decode_info* info,
-                                uint64_t* status, void* workspace, const void* d_tables, hipStream_t s);
+                         void* workspace, const unscan::HuffBlob* blob, hipStream_t s);
 // the marker search's launches alone (count, rank, place; the rank launch alone with offsets), for hpdct_unscan_split.hpp
 hipError_t launch_unscan_locate(const uint8_t* scan, uint64_t bytes, const uint64_t* offs, const scan::ScanGrid& g,
                                 hpdct_decode_info* info, void* workspace, hipStream_t s);
@@ -382,15 +400,7 @@ hipError_t launch_unscan_locate(const uint8_t* scan, uint64_t bytes, const uint6
 namespace hpdct {
 
 __device__ const unscan::DecodeTables kUnscanTables = unscan::make_decode_tables();
-struct UnscanOrder {
-    uint8_t v[64];
-};
-constexpr UnscanOrder make_unscan_order() {
-    UnscanOrder o{};
-    for (int n = 0; n < 64; ++n) o.v[n] = zigzag::kOrder[n];
-    return o;
-}
-__device__ const UnscanOrder kUnscanOrder = make_unscan_order();
+__device__ const unscan::ZigzagOrder kUnscanOrder = unscan::make_zigzag_order();
 
 __device__ inline uint32_t unscan_wave_sum(uint32_t v) {
 #pragma unroll

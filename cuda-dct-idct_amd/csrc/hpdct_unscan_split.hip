@@ -1,4 +1,5 @@
-// hpdct_unscan_split.hip -- the split entropy decoder's kernels and launches (hpdct_unscan_split.hpp).
+// hpdct_unscan_split.hip -- the split entropy decoder's kernels and launches (hpdct_unscan_split.hpp): one launch
+// function, launch_unscan_split, for Annex K's tables and the caller's.
 #include "hpdct_unscan_split.hpp"
 #include "hpdct_launch.hpp"
 
@@ -13,15 +14,7 @@ using unsplit::Ws;
 constexpr uint32_t kG = unsplit::kGroup, kS = unsplit::kSegBytes;
 
 __device__ const unscan::DecodeTables kUnsplitTables = unscan::make_decode_tables();
-struct UnsplitOrder {
-    uint8_t v[64];
-};
-constexpr UnsplitOrder make_unsplit_order() {
-    UnsplitOrder o{};
-    for (int n = 0; n < 64; ++n) o.v[n] = zigzag::kOrder[n];
-    return o;
-}
-__device__ const UnsplitOrder kUnsplitOrder = make_unsplit_order();
+__device__ const unscan::ZigzagOrder kUnsplitOrder = unscan::make_zigzag_order();
 
 // what every kernel gets of the call
 struct Call {
@@ -390,35 +383,24 @@ __global__ __launch_bounds__(64) void unsplit_serial_tables_kernel(const Call c,
     unsplit_serial_body<kVar, unscan::DecodeTablesWide>(c, ws, y, cb, cr, info, status, blob_tables(blob));
 }
 
-// blob == nullptr: Annex K's kernels
-template <unsigned kLaneBit>
-hipError_t launch_serial(const policy::Choice& ch, hipStream_t s, const Call& c, const Ws& ws, int16_t* y, int16_t* cb,
-                         int16_t* cr, hpdct_decode_split_info* info, uint64_t* status, const unscan::HuffBlob* blob) {
-    return policy::with_bit<kScanNatural, true>(ch.var, [&](auto kN) {
-        constexpr unsigned kV = with_block<64>(kUnsplitSerial | decltype(kN)::value | kLaneBit);
-        if (blob)
-            return launch_choice<(kV | kScanTables), unsplit_serial_tables_kernel<(kV | kScanTables)>>(
-                ch, s, c, ws, y, cb, cr, info, status, blob);
-        return launch_choice<kV, unsplit_serial_kernel<kV>>(ch, s, c, ws, y, cb, cr, info, status);
-    });
+// The pick between the two instantiations of a kernel, for each of the three launches that read the Huffman
+// tables: kTables, of variant kV | kScanTables, reads the caller's blob, its last argument; kBuiltin, of variant
+// kV, holds Annex K's (blob nullptr).  kTables is named first, as the code object holds the pair
+// (profiles/r14/README.md).
+template <unsigned kV, auto kTables, auto kBuiltin, typename... Args>
+hipError_t launch_choice_tables(const policy::Choice& ch, hipStream_t s, const unscan::HuffBlob* blob,
+                                const Args&... args) {
+    if (blob) return launch_choice<(kV | kScanTables), kTables>(ch, s, args..., blob);
+    return launch_choice<kV, kBuiltin>(ch, s, args...);
 }
 
 }  // namespace
 
 hipError_t launch_unscan_split(const uint8_t* scan, uint64_t bytes, const uint64_t* offs, int16_t* y, int16_t* cb,
                                int16_t* cr, const scan::ScanGrid& g, bool natural, uint64_t split_min,
-                               hpdct_decode_split_info* info, uint64_t* status, void* workspace, hipStream_t s) {
-    return launch_unscan_split_tables(scan, bytes, offs, y, cb, cr, g, natural, split_min, info, status, workspace,
-                                      nullptr, s);
-}
-
-hipError_t launch_unscan_split_tables(const uint8_t* scan, uint64_t bytes, const uint64_t* offs, int16_t* y,
-                                      int16_t* cb, int16_t* cr, const scan::ScanGrid& g, bool natural,
-                                      uint64_t split_min, hpdct_decode_split_info* info, uint64_t* status,
-                                      void* workspace, const void* d_tables, hipStream_t s) {
-    const unscan::HuffBlob* blob = static_cast<const unscan::HuffBlob*>(d_tables);
+                               hpdct_decode_split_info* info, uint64_t* status, void* workspace,
+                               const unscan::HuffBlob* blob, hipStream_t s) {
     const bool tables = blob != nullptr;
-    constexpr unsigned kSettleT = with_block<256>(kUnsplitSettle | kScanTables);
     if (hipError_t e = launch_unscan_locate(scan, bytes, offs, g, reinterpret_cast<hpdct_decode_info*>(info), workspace, s))
         return e;
     const unsplit::Layout lay = unsplit::layout(g.intervals, bytes);
@@ -428,10 +410,8 @@ hipError_t launch_unscan_split_tables(const uint8_t* scan, uint64_t bytes, const
     constexpr unsigned kOffsetsV = with_block<256>(kUnsplitOffsets), kClearV = with_block<256>(kUnsplitClear);
     if (hipError_t e = launch_choice<kPlanV, unsplit_plan_kernel>(policy::unsplit_plan(), s, c, ws, info)) return e;
     for (uint32_t launch = 0; launch <= unsplit::kRounds; ++launch)
-        if (hipError_t e = tables ? launch_choice<kSettleT, unsplit_settle_tables_kernel>(
-                                        policy::unsplit_settle(lay.ngrp, true), s, c, ws, launch, info, blob)
-                                  : launch_choice<kSettleV, unsplit_settle_kernel>(policy::unsplit_settle(lay.ngrp), s, c,
-                                                                                   ws, launch, info))
+        if (hipError_t e = launch_choice_tables<kSettleV, unsplit_settle_tables_kernel, unsplit_settle_kernel>(
+                policy::unsplit_settle(lay.ngrp, tables), s, blob, c, ws, launch, info))
             return e;
     if (hipError_t e = launch_choice<kOffsetsV, unsplit_offsets_kernel>(policy::unsplit_offsets(g.intervals), s, c, ws, info))
         return e;
@@ -442,21 +422,20 @@ hipError_t launch_unscan_split_tables(const uint8_t* scan, uint64_t bytes, const
     const policy::Choice cw = policy::unsplit_write(lay.ngrp, natural, tables);
     if (hipError_t e = policy::with_bit<kScanNatural, true>(cw.var, [&](auto kN) {
             constexpr unsigned kV = with_block<256>(kUnsplitWrite | decltype(kN)::value);
-            if (tables)
-                return launch_choice<(kV | kScanTables), unsplit_write_tables_kernel<(kV | kScanTables)>>(
-                    cw, s, c, ws, y, cb, cr, cinfo, blob);
-            return launch_choice<kV, unsplit_write_kernel<kV>>(cw, s, c, ws, y, cb, cr, cinfo);
+            return launch_choice_tables<kV, unsplit_write_tables_kernel<(kV | kScanTables)>, unsplit_write_kernel<kV>>(
+                cw, s, blob, c, ws, y, cb, cr, cinfo);
         }))
         return e;
     policy::UnscanCall pc;
     pc.intervals = g.intervals, pc.natural = natural, pc.tables = tables;
     const policy::Choice cs = policy::unsplit_serial(pc);
-    switch (unscan_lanes_of(cs.var)) {
-        case 1u: return launch_serial<kUnscanLanes1>(cs, s, c, ws, y, cb, cr, info, status, blob);
-        case 4u: return launch_serial<kUnscanLanes4>(cs, s, c, ws, y, cb, cr, info, status, blob);
-        case 16u: return launch_serial<kUnscanLanes16>(cs, s, c, ws, y, cb, cr, info, status, blob);
-        default: return launch_serial<0u>(cs, s, c, ws, y, cb, cr, info, status, blob);
-    }
+    return with_lanes(cs.var, [&](auto kL) {
+        return policy::with_bit<kScanNatural, true>(cs.var, [&](auto kN) {
+            constexpr unsigned kV = with_block<64>(kUnsplitSerial | decltype(kN)::value | decltype(kL)::value);
+            return launch_choice_tables<kV, unsplit_serial_tables_kernel<(kV | kScanTables)>, unsplit_serial_kernel<kV>>(
+                cs, s, blob, c, ws, y, cb, cr, info, status);
+        });
+    });
 }
 
 }  // namespace hpdct

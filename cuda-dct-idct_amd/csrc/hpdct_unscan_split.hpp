@@ -283,14 +283,11 @@ HPDCT_HD bool ends_clean(const SegState& last, uint64_t hi) { return last.pos ==
 }  // namespace unsplit
 
 // The launches on s (hpdct_unscan_split.hip).  workspace: unsplit::layout(g.intervals, bytes).bytes bytes, 16-byte
-// aligned; split_min >= 1.  The caller checked everything.
+// aligned; split_min >= 1.  blob nullptr: Annex K's kernels; else the caller's tables, a HuffBlob
+// (hpdct_unscan.hpp) in device memory.  The caller checked everything.
 hipError_t launch_unscan_split(const uint8_t* scan, uint64_t bytes, const uint64_t* offs, int16_t* y, int16_t* cb,
                                int16_t* cr, const scan::ScanGrid& g, bool natural, uint64_t split_min,
-                               hpdct_decode_split_info* info, uint64_t* status, void* workspace, hipStream_t s);
-// the same under the caller's tables: d_tables a HuffBlob (hpdct_unscan.hpp) in device memory, or nullptr for Annex K
-hipError_t launch_unscan_split_tables(const uint8_t* scan, uint64_t bytes, const uint64_t* offs, int16_t* y,
-                                      int16_t* cb, int16_t* cr, const scan::ScanGrid& g, bool natural,
-                                      uint64_t split_min, hpdct_decode_split_info* info, uint64_t* status,
-                                      void* workspace, const void* d_tables, hipStream_t s);
+                               hpdct_decode_split_info* info, uint64_t* status, void* workspace,
+                               const unscan::HuffBlob* blob, hipStream_t s);
 
 }  // namespace hpdct

@@ -1,7 +1,7 @@
 // hpdct_zigzag.h -- the JPEG zig-zag scan of an 8x8 block, one copy for the
 // host (hpdct_zigzag_order) and the block kernels (hpdct_blocks.hpp), which
-// index it with compile-time constants only.  Plain C++: hpdct_api.cpp includes
-// it under g++ too.
+// index it with compile-time constants only.  Plain C++: hpdct_api.cpp and
+// hpdct_api_jpeg.cpp include it under g++ too.
 #pragma once
 
 namespace hpdct {

@@ -814,13 +814,17 @@ def bind_rgb_frame(direction: str, rgb, y, cb, cr, *, subsampling: str = "420", 
 HUFFMAN_TABLES = {"dc_luma": 0, "ac_luma": 1, "dc_chroma": 2, "ac_chroma": 3}
 
 
-def scan_bound(blocks: int, intervals: int) -> int:
-    """Worst-case bytes of a scan of `blocks` blocks in `intervals` restart
-    intervals (hpdct_scan_bound): 415 * blocks + 4 * intervals."""
-    n = int(load_library().hpdct_scan_bound(int(blocks), int(intervals)))
+def _scan_bound(entry: str, blocks: int, intervals: int) -> int:
+    n = int(getattr(load_library(), entry)(int(blocks), int(intervals)))
     if n < 0:
         raise HpdctError(1, f"no scan bound for {blocks} blocks in {intervals} intervals")
     return n
+
+
+def scan_bound(blocks: int, intervals: int) -> int:
+    """Worst-case bytes of a scan of `blocks` blocks in `intervals` restart
+    intervals (hpdct_scan_bound): 415 * blocks + 4 * intervals."""
+    return _scan_bound("hpdct_scan_bound", blocks, intervals)
 
 
 def huffman_table(kind):
@@ -889,10 +893,7 @@ def huffman_optimal(counts):
 
 def scan_bound_tables(blocks: int, intervals: int) -> int:
     """scan_bound under a caller's tables (hpdct_scan_bound_tables): 417 * blocks + 4 * intervals."""
-    n = int(load_library().hpdct_scan_bound_tables(int(blocks), int(intervals)))
-    if n < 0:
-        raise HpdctError(1, f"no scan bound for {blocks} blocks in {intervals} intervals")
-    return n
+    return _scan_bound("hpdct_scan_bound_tables", blocks, intervals)
 
 
 def _tables_ptr(tables, device):
@@ -915,11 +916,8 @@ def jpeg_header(height: int, width: int, *, components: int = 3, subsampling: st
     args = (buf.ctypes.data, buf.size, ctypes.addressof(n), int(height), int(width), int(components),
             _subsampling(subsampling), None if ql is None else ql.ctypes.data,
             None if qc is None else qc.ctypes.data, int(restart_interval))
-    if tables is None:
-        _check(load_library().hpdct_jpeg_header(*args))
-    else:
-        arr = _huffman_specs(tables)
-        _check(load_library().hpdct_jpeg_header_tables(*args, ctypes.addressof(arr)))
+    arr = None if tables is None else _huffman_specs(tables)
+    _check(load_library().hpdct_jpeg_header_tables(*args, None if arr is None else ctypes.addressof(arr)))
     return buf[:n.value].tobytes()
 
 
@@ -974,9 +972,7 @@ def bind_scan(y, cb, cr, scan, info, offsets, workspace, *, height=None, width=N
     args = (vp(y.data_ptr()), None if cb is None else vp(cb.data_ptr()), None if cr is None else vp(cr.data_ptr()),
             h, w, sub, int(restart_interval), flags, vp(scan.data_ptr()), cap, vp(info.data_ptr()),
             None if offsets is None else vp(offsets.data_ptr()), vp(workspace.data_ptr()), workspace.numel())
-    if tables is not None:
-        return _bound(load_library().hpdct_encode_scan_tables, args + (_tables_ptr(tables, y.device), _stream_ptr(stream)))
-    return _bound(load_library().hpdct_encode_scan, args + (_stream_ptr(stream),))
+    return _bound(load_library().hpdct_encode_scan_tables, args + (_tables_ptr(tables, y.device), _stream_ptr(stream)))
 
 
 def bind_scan_histogram(y, cb, cr, counts, *, height=None, width=None, subsampling: str = "420",
@@ -1101,21 +1097,30 @@ class _JpegLayout(ctypes.Structure):  # hpdct_jpeg_layout
                 ("scan_bytes", ctypes.c_int64), ("q_luma", ctypes.c_float * 64), ("q_chroma", ctypes.c_float * 64)]
 
 
+def _jpeg_parse(data, specs) -> dict:
+    """jpeg_parse (specs None) and jpeg_parse_tables (specs: the hpdct_huffman_spec[4] to fill): the layout as a
+    dictionary."""
+    buf = np.frombuffer(bytes(data), np.uint8)
+    lay = _JpegLayout()
+    args = (buf.ctypes.data if buf.size else ctypes.addressof(lay), buf.size, ctypes.addressof(lay))
+    if specs is None:
+        _check(load_library().hpdct_jpeg_parse(*args))
+    else:
+        _check(load_library().hpdct_jpeg_parse_tables(*args, ctypes.addressof(specs)))
+    names = {v: k for k, v in SUBSAMPLINGS.items()}
+    return {"height": lay.height, "width": lay.width, "components": lay.components, "subsampling": names[lay.sub],
+            "restart_interval": lay.restart_interval, "scan_offset": lay.scan_offset, "scan_bytes": lay.scan_bytes,
+            "q_luma": np.array(lay.q_luma, np.float32).reshape(8, 8),
+            "q_chroma": np.array(lay.q_chroma, np.float32).reshape(8, 8) if lay.components == 3 else None}
+
+
 def jpeg_parse(data) -> dict:
     """SOI .. SOS of a baseline file (hpdct_jpeg_parse, host only): {"height",
     "width" (the TRUE frame size), "components", "subsampling", "restart_interval",
     "scan_offset", "scan_bytes", "q_luma", "q_chroma" (8x8 float32, row-major;
     q_chroma None for one component)}.  HpdctError status 2 names why a file is
     not one decode_scan decodes, status 1 a truncated or malformed file."""
-    buf = np.frombuffer(bytes(data), np.uint8)
-    lay = _JpegLayout()
-    _check(load_library().hpdct_jpeg_parse(buf.ctypes.data if buf.size else ctypes.addressof(lay), buf.size,
-                                           ctypes.addressof(lay)))
-    names = {v: k for k, v in SUBSAMPLINGS.items()}
-    return {"height": lay.height, "width": lay.width, "components": lay.components, "subsampling": names[lay.sub],
-            "restart_interval": lay.restart_interval, "scan_offset": lay.scan_offset, "scan_bytes": lay.scan_bytes,
-            "q_luma": np.array(lay.q_luma, np.float32).reshape(8, 8),
-            "q_chroma": np.array(lay.q_chroma, np.float32).reshape(8, 8) if lay.components == 3 else None}
+    return _jpeg_parse(data, None)
 
 
 def jpeg_parse_tables(data) -> dict:
@@ -1124,17 +1129,8 @@ def jpeg_parse_tables(data) -> dict:
     (bits, vals) pairs the scan's components select (DC luma, AC luma, DC
     chroma, AC chroma; the chroma pair empty for one component), as
     huffman_prepare takes them."""
-    buf = np.frombuffer(bytes(data), np.uint8)
-    lay = _JpegLayout()
     arr = (_HuffmanSpec * 4)()
-    _check(load_library().hpdct_jpeg_parse_tables(buf.ctypes.data if buf.size else ctypes.addressof(lay), buf.size,
-                                                  ctypes.addressof(lay), ctypes.addressof(arr)))
-    names = {v: k for k, v in SUBSAMPLINGS.items()}
-    return {"height": lay.height, "width": lay.width, "components": lay.components, "subsampling": names[lay.sub],
-            "restart_interval": lay.restart_interval, "scan_offset": lay.scan_offset, "scan_bytes": lay.scan_bytes,
-            "q_luma": np.array(lay.q_luma, np.float32).reshape(8, 8),
-            "q_chroma": np.array(lay.q_chroma, np.float32).reshape(8, 8) if lay.components == 3 else None,
-            "tables": _specs_out(arr)}
+    return dict(_jpeg_parse(data, arr), tables=_specs_out(arr))
 
 
 def _decode_geometry(height, width, components, sub: int, restart_interval):
@@ -1201,10 +1197,8 @@ def _bind_decode(split_min_bytes, scan, offsets, y, cb, cr, info, status, worksp
             vp(info.data_ptr()), None if status is None else vp(status.data_ptr()),
             vp(workspace.data_ptr()), workspace.numel())
     lib = load_library()
-    if tables is not None:
-        return _bound(lib.hpdct_decode_scan_split_tables if split else lib.hpdct_decode_scan_tables,
-                      args + (_tables_ptr(tables, y.device), _stream_ptr(stream)))
-    return _bound(lib.hpdct_decode_scan_split if split else lib.hpdct_decode_scan, args + (_stream_ptr(stream),))
+    return _bound(lib.hpdct_decode_scan_split_tables if split else lib.hpdct_decode_scan_tables,
+                  args + (_tables_ptr(tables, y.device), _stream_ptr(stream)))
 
 
 def bind_decode_scan(scan, offsets, y, cb, cr, info, status, workspace, *, height=None, width=None,

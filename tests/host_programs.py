@@ -38,14 +38,15 @@ def policy_check(name, tmp_path):
 
 
 def sanitised_check(name, tmp_path, kernel_object):
-    """tests/tools/<name>.cpp with hpdct_api.cpp under asan.mk's ASan + UBSan flags and the library's kernel
-    objects linked as they are (host registration stubs only); kernel_object names one that must be among them."""
+    """tests/tools/<name>.cpp with the C ABI's host sources (asan.mk's HOST list) under asan.mk's ASan + UBSan flags
+    and the library's kernel objects linked as they are (host registration stubs only); kernel_object names one
+    that must be among them."""
     kobj = asan_mk("KOBJ")
     want = [line.split(":=")[1].split() for line in open(os.path.join(PKG, "Makefile")) if line.startswith("KOBJ")][0]
     assert len(kobj) == len(want) and any(o.endswith(kernel_object) for o in kobj), \
         "library objects not built (__graft_entry__.build())"
     r = _build_and_run(name, tmp_path, asan_mk("CXXF"),
-                       [os.path.join(PKG, "csrc", "hpdct_api.cpp")] + kobj +
+                       [os.path.join(PKG, "csrc", h + ".cpp") for h in asan_mk("HOST")] + kobj +
                        ["-L/opt/rocm/lib", "-Wl,-rpath,/opt/rocm/lib", "-lamdhip64", "-lpthread", "-lm"], 600, 120,
                        env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0:halt_on_error=1",
                                 UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1"))

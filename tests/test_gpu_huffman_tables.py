@@ -1,7 +1,8 @@
 """GPU tests of the caller's Huffman tables: hpdct_scan_histogram,
 hpdct_encode_scan_tables and hpdct_decode_scan_tables, exactly against their
 plain-Python restatement in tests/jpeg_tables.py; the optimised files of another
-writer (tests/golden/pillow_opt_*.jpg) and of jpeg_encode(optimize=True).
+writer (tests/golden/pillow_opt_*.jpg) and of jpeg_encode(optimize=True); the
+decoders' lane dispatch at interval counts on both sides of its thresholds.
 """
 import io
 import os
@@ -323,6 +324,64 @@ def test_decode_corrupt_corpus(hp, dev):
                 wrong += not _check_decode(hp, dev, scan, sampling, shapes, ri, other, _blob(hp, dev, other))
     print("corrupt corpus under the caller's tables: %d cases in %.2f s" % (cases, time.perf_counter() - t0))
     assert cases >= 150 and wrong == 0
+
+
+# ---------------------------------------------------------------------------
+# the lane dispatch of the serial decoder and of the split decoder's serial launch
+# ---------------------------------------------------------------------------
+def _encode_unsuffixed(hp, y, h, w, capacity):
+    """hpdct_encode_scan itself on grey blocks with restart_interval 1, past the binding (which calls
+    hpdct_encode_scan_tables with NULL tables): the scan's bytes."""
+    import ctypes
+    import torch
+    lib, vp = hp.load_library(), ctypes.c_void_p
+    ws_bytes = int(lib.hpdct_scan_workspace_bytes(h, w, 1, hp.SUBSAMPLINGS["444"], 1))
+    assert ws_bytes > 0
+    scan = torch.empty(capacity, dtype=torch.uint8, device=y.device)
+    info = torch.empty(2, dtype=torch.int64, device=y.device)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=y.device)
+    st = lib.hpdct_encode_scan(vp(y.data_ptr()), None, None, h, w, hp.SUBSAMPLINGS["444"], 1, 0, vp(scan.data_ptr()),
+                               capacity, vp(info.data_ptr()), None, vp(ws.data_ptr()), ws_bytes,
+                               vp(torch.cuda.current_stream().cuda_stream))
+    assert st == 0, lib.hpdct_last_error_string()
+    res = hp.scan_info(info)
+    assert res["truncated"] == 0
+    return scan[:res["bytes"]]
+
+
+@pytest.mark.parametrize("lanes,h,w", [(1, 8, 512), (4, 8, 65544), (16, 16, 65544), (64, 2048, 2056)],
+                         ids=["1-lane", "4-lanes", "16-lanes", "64-lanes"])
+def test_lane_dispatch_round_trip(hp, dev, lanes, h, w):
+    """Grey frames of one 8x8 block per restart interval, their interval counts (64, 8,193, 16,386, 65,792) on both
+    sides of the policy's thresholds (8,192, 16,384, 65,536), so that each of the 1 / 4 / 16 / 64-lane decode kernels
+    is the one launched: a kernel picked with the wrong stride leaves intervals undecoded or decodes them twice.
+    Seeded blocks, every coefficient within +-1023, three AC positions a block.  encode_scan, then decode_scan and
+    decode_scan_split with a split_min_bytes no interval reaches (every interval goes to its serial launch), under
+    Annex K's tables (tables=None) and under the optimal tables of the frame's own histogram."""
+    import torch
+    n = (h // 8) * (w // 8)
+    want_lanes = 1 if n <= 8192 else 4 if n <= 16384 else 16 if n <= 65536 else 64
+    assert want_lanes == lanes                      # hpdct_policy.hpp's unscan_lanes, restated
+    rng = np.random.default_rng(1400 + lanes)
+    b = np.zeros((n, 64), np.int16)
+    b[:, 0] = rng.integers(-1023, 1024, n)
+    np.put_along_axis(b, rng.integers(1, 64, (n, 3)), rng.integers(-1023, 1024, (n, 3)).astype(np.int16), 1)
+    y = _dev(b.reshape(h // 8, w // 8, 64), dev)
+    counts = hp.scan_histogram(y, restart_interval=1).cpu().numpy()
+    optimal = _blob(hp, dev, [hp.huffman_optimal(counts[0]), hp.huffman_optimal(counts[1]), None, None])
+    for tables in (None, optimal):
+        scan, info, offs = hp.encode_scan(y, restart_interval=1, tables=tables)
+        assert info["truncated"] == 0 and info["out_of_range"] == 0
+        if tables is None:
+            assert torch.equal(scan, _encode_unsuffixed(hp, y, h, w, scan.numel() + 16))
+        for method in ("serial", "split"):
+            (got,), dinfo, status = hp.decode_scan(scan, height=h, width=w, components=1, restart_interval=1,
+                                                   offsets=offs, tables=tables, method=method,
+                                                   split_min_bytes=1 << 40)
+            assert torch.equal(got, y), (method, tables is not None)
+            assert not bool(status.any()) and dinfo["bad_intervals"] == 0
+            if method == "split":
+                assert dinfo["serial_intervals"] == n and dinfo["split_intervals"] == 0
 
 
 # ---------------------------------------------------------------------------

@@ -427,6 +427,6 @@ def test_scan_policy_rows(tmp_path):
 # ---------------------------------------------------------------------------
 def test_scan_validation_clean_under_asan_ubsan(tmp_path):
     """A stand-alone program (tests/tools/asan_scan_check.cpp, its own main) drives hpdct_encode_scan's refusals
-    and hpdct_jpeg_header with hpdct_api.cpp compiled by g++ under tests/tools/asan.mk's ASan + UBSan flags and the
+    and hpdct_jpeg_header with the C ABI's host sources (tests/tools/asan.mk's HOST) compiled by g++ under tests/tools/asan.mk's ASan + UBSan flags and the
     library's kernel objects linked as they are.  CPU only: nothing is launched, nothing is loaded into Python."""
     host_programs.sanitised_check("asan_scan_check", tmp_path, "hpdct_scan.o")

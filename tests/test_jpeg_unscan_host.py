@@ -363,7 +363,7 @@ def test_unscan_policy_rows(tmp_path):
 # the refusals, the parser and the walker under ASan + UBSan
 # ---------------------------------------------------------------------------
 def test_unscan_clean_under_asan_ubsan(tmp_path):
-    """A stand-alone program (tests/tools/asan_unscan_check.cpp, its own main) with hpdct_api.cpp compiled by g++
+    """A stand-alone program (tests/tools/asan_unscan_check.cpp, its own main) with the C ABI's host sources (tests/tools/asan.mk's HOST) compiled by g++
     under tests/tools/asan.mk's ASan + UBSan flags: hpdct_decode_scan's refusals, hpdct_jpeg_parse on every
     truncation and corruption of a file, and unscan::walk_interval -- the function the decode kernel wraps -- over
     the whole corpus (grey and colour) and the built scans of tests/unscan_built.py, each at the eight addresses

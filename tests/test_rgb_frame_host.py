@@ -176,7 +176,7 @@ def test_rgb_frame_policy_table(tmp_path):
 
 def test_frame_validation_clean_under_asan_ubsan(tmp_path):
     """A stand-alone program (tests/tools/asan_rgb_frame_check.cpp, its own main) drives the validation paths
-    with hpdct_api.cpp compiled by g++ under tests/tools/asan.mk's ASan + UBSan flags and the library's kernel
+    with the C ABI's host sources (tests/tools/asan.mk's HOST) compiled by g++ under tests/tools/asan.mk's ASan + UBSan flags and the library's kernel
     objects linked as they are.  CPU only: nothing is launched, nothing is loaded into Python."""
     host_programs.sanitised_check("asan_rgb_frame_check", tmp_path, "hpdct_rgb_fwd420_clip.o")
 

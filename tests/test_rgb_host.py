@@ -138,7 +138,7 @@ _KOBJ = os.path.join(host_programs.PKG, "build", "hpdct_rgb_inv.o")
 @pytest.mark.skipif(not os.path.exists(_KOBJ), reason="library objects not built (__graft_entry__.build())")
 def test_rgb_validation_clean_under_asan_ubsan(tmp_path):
     """A stand-alone program (tests/tools/asan_rgb_check.cpp) drives the new validation paths with
-    hpdct_api.cpp compiled by g++ under ASan + UBSan and the library's kernel objects linked as they are
+    the C ABI's host sources (tests/tools/asan.mk's HOST) compiled by g++ under ASan + UBSan and the library's kernel objects linked as they are
     (the Makefile's KOBJ line).  CPU only: nothing is launched."""
     host_programs.sanitised_check("asan_rgb_check", tmp_path, "hpdct_rgb_inv.o")
 

@@ -1,6 +1,6 @@
 """Host code under AddressSanitizer + UndefinedBehaviorSanitizer (SURVEY.md
 section 5).  CPU only, no GPU: tests/tools/asan.mk builds the C-ABI host
-sources (hpdct_api.cpp, hpdct_compat.cpp, hpdct_stream.cpp), the oracle and
+sources (hpdct_api.cpp, hpdct_api_jpeg.cpp, hpdct_compat.cpp, hpdct_stream.cpp), the oracle and
 host/image_io.hpp with g++ -fsanitize=address,undefined into
 build/asan/asan_host_check, which drives every host path that runs without a
 device (helpers, quant-table mutex from 8 threads, argument validation of

@@ -230,7 +230,7 @@ def test_unscan_split_policy_rows(tmp_path):
 
 
 def test_unscan_split_clean_under_asan_ubsan(tmp_path):
-    """A stand-alone program (tests/tools/asan_unscan_split_check.cpp, its own main) with hpdct_api.cpp compiled by
+    """A stand-alone program (tests/tools/asan_unscan_split_check.cpp, its own main) with the C ABI's host sources (tests/tools/asan.mk's HOST) compiled by
     g++ under tests/tools/asan.mk's ASan + UBSan flags: hpdct_decode_scan_split's refusals, and the whole algorithm
     on the CPU -- lanes as loops over unsplit::walk_segment, the function the kernels call -- over the corpus, the
     built scans and the split inputs, every array of the workspace in a heap buffer of exactly its budget, each scan

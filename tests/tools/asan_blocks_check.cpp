@@ -1,6 +1,6 @@
 // asan_blocks_check.cpp -- drives the validation paths of hpdct_forward_blocks /
 // hpdct_inverse_blocks and hpdct_zigzag_order under ASan + UBSan, CPU only: a
-// stand-alone program linked with the sanitised hpdct_api.cpp (g++) and the
+// stand-alone program linked with the sanitised host sources of the C ABI (g++; asan.mk's HOST) and the
 // library's kernel objects, as tests/tools/asan.mk links asan_host_check.  No
 // kernel is launched: every call here fails its checks (or touches host
 // memory only).  Built and run by tests/test_blocks_host.py.

@@ -1,5 +1,5 @@
 // asan_huffman_check.cpp -- the caller's Huffman tables under ASan + UBSan, CPU
-// only: a stand-alone program linked with the sanitised hpdct_api.cpp (g++) and
+// only: a stand-alone program linked with the sanitised host sources of the C ABI (g++; asan.mk's HOST) and
 // the library's kernel objects, as asan_unscan_check.cpp is.  No kernel is
 // launched.  DHT contents and table blobs are untrusted, so:
 //   1. hpdct_huffman_prepare, hpdct_huffman_optimal and hpdct_jpeg_parse_tables

@@ -1,7 +1,7 @@
 // asan_rgb_check.cpp -- drives the validation paths of hpdct_forward_rgb_blocks /
 // hpdct_inverse_rgb_blocks and hpdct_default_chroma_quant_table under ASan +
 // UBSan, CPU only: a stand-alone program linked with the sanitised
-// hpdct_api.cpp (g++) and the library's kernel objects, as asan_blocks_check.cpp
+// the C ABI's host sources (g++; asan.mk's HOST) and the library's kernel objects, as asan_blocks_check.cpp
 // is.  No kernel is launched: every call here fails its checks (or touches host
 // memory only).  Built and run by tests/test_rgb_host.py.
 #include <cmath>

@@ -1,7 +1,7 @@
 // asan_rgb_frame_check.cpp -- drives the validation paths of
 // hpdct_rgb_frame_geometry, hpdct_forward_rgb_frame and hpdct_inverse_rgb_frame
 // under ASan + UBSan, CPU only: a stand-alone program linked with the sanitised
-// hpdct_api.cpp (g++) and the library's kernel objects, as asan_rgb_check.cpp
+// the C ABI's host sources (g++; asan.mk's HOST) and the library's kernel objects, as asan_rgb_check.cpp
 // is.  No kernel is launched: every device call here fails its checks first.
 // Built and run by tests/test_rgb_frame_host.py.
 #include <cmath>

@@ -1,8 +1,9 @@
 // asan_scan_check.cpp -- drives the validation paths of hpdct_encode_scan, the
 // host calls beside it (hpdct_scan_bound, hpdct_scan_workspace_bytes,
 // hpdct_huffman_table) and the header writer hpdct_jpeg_header under ASan +
-// UBSan, CPU only: a stand-alone program linked with the sanitised hpdct_api.cpp
-// (g++) and the library's kernel objects, as asan_rgb_frame_check.cpp is.  No
+// UBSan, CPU only: a stand-alone program linked with the sanitised host sources
+// of the C ABI (g++; asan.mk's HOST) and the library's kernel objects, as
+// asan_rgb_frame_check.cpp is.  No
 // kernel is launched: every device call here fails its checks first.
 // Built and run by tests/test_jpeg_scan_host.py.
 #include <cmath>

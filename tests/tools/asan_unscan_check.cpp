@@ -1,5 +1,5 @@
 // asan_unscan_check.cpp -- the entropy decoder's host side under ASan + UBSan,
-// CPU only: a stand-alone program linked with the sanitised hpdct_api.cpp (g++)
+// CPU only: a stand-alone program linked with the sanitised host sources of the C ABI (g++; asan.mk's HOST)
 // and the library's kernel objects, as asan_scan_check.cpp is.  No kernel is
 // launched: every device call here fails its checks first.
 //   1. the refusals of hpdct_decode_scan and hpdct_decode_workspace_bytes;

@@ -1,5 +1,5 @@
 // asan_unscan_split_check.cpp -- the split entropy decoder under ASan + UBSan,
-// CPU only: a stand-alone program linked with the sanitised hpdct_api.cpp (g++)
+// CPU only: a stand-alone program linked with the sanitised host sources of the C ABI (g++; asan.mk's HOST)
 // and the library's kernel objects, as asan_unscan_check.cpp is.  No kernel is
 // launched: every device call here fails its checks first.
 //   1. the refusals of hpdct_decode_scan_split and
