@@ -6,6 +6,7 @@
 #include <type_traits>
 
 #include "hpdct.h"
+#include "hpdct_grey_frame.h"
 #include "hpdct_kernels.h"
 
 namespace hpdct {
@@ -18,7 +19,8 @@ namespace policy {
 // kScan: scan_code_kernel / scan_offsets_kernel (hpdct_scan.hpp)
 // kUnscan: unscan_locate_kernel / unscan_rank_kernel / unscan_decode_kernel (hpdct_unscan.hpp)
 // kUnsplit: the unsplit_*_kernel of hpdct_unscan_split.hip
-enum class Family { kTile, kOctet, kDuo, kDuoFwdU8, kRowFirstDuo, kRtDuo, kRtTile, kBlocks, kRgb, kScan, kUnscan, kUnsplit };
+// kGrey: fdct_grey_frame_kernel / idct_grey_frame_kernel (hpdct_grey_frame.hpp)
+enum class Family { kTile, kOctet, kDuo, kDuoFwdU8, kRowFirstDuo, kRtDuo, kRtTile, kBlocks, kRgb, kScan, kUnscan, kUnsplit, kGrey };
 enum class Elem { kU8, kI8, kF32 };
 
 // var: the kernel's kVar; kDuoFwdU8 and kRt* carry their quotient and straddle bits there
@@ -311,6 +313,33 @@ inline Choice inverse_blocks(const Call& c) {
     if (c.full_chain) return uncapped(Family::kBlocks, kInvFullVar, tile_waves(c.g));
     const bool straddle = c.out == Elem::kF32 && c.g.tiles_x % 64u != 0u;
     return uncapped(Family::kBlocks, blocks_inv_var(c.out) | (straddle ? kVarStraddle : 0u), tile_waves(c.g));
+}
+
+// Grey frames of any size and row pitch (hpdct_grey_frame.hpp): the blocks rows
+// above over the PADDED tile grid, the same workgroup size, non-temporal stores
+// and LDS-staged forward; hpdct_set_mapping is not read.
+struct GreyCall {
+    uint32_t tiles = 0;  // the padded tile grid's
+    int qmode = 0;       // forward only
+    // clip: the frame is not whole tiles, or its base or row pitch is not 8-byte
+    // aligned (grey_whole_aligned is false): the same launch shape with kGreyClip,
+    // the kernels' general instantiation.  A speed decision only: both
+    // instantiations give a whole aligned frame the same bytes.
+    bool clip = false;
+    // inverse only: the table fails the skip criterion for int16 blocks (kVarFullChain)
+    bool full_chain = false;
+};
+constexpr uint32_t grey_waves(const GreyCall& c) { return c.tiles / 64u + (c.tiles % 64u != 0u); }
+constexpr unsigned kGreyFwdVar = kBlocksFwdVar;
+inline Choice forward_grey(const GreyCall& c) {
+    return uncapped(Family::kGrey, kGreyFwdVar | quot_bits(c.qmode) | (c.clip ? kGreyClip : 0u), grey_waves(c));
+}
+// Inverse: uint8 pixels only; per-lane 8-byte row stores, as the blocks inverse to uint8
+constexpr unsigned kGreyInvVar = blocks_inv_var(Elem::kU8);
+inline Choice inverse_grey(const GreyCall& c) {
+    // the full chain: one instantiation, the general one (kGreyClip takes whole aligned frames too)
+    if (c.full_chain) return uncapped(Family::kGrey, kInvFullVar | kGreyClip, grey_waves(c));
+    return uncapped(Family::kGrey, kGreyInvVar | (c.clip ? kGreyClip : 0u), grey_waves(c));
 }
 
 // Colour frames (hpdct_rgb.hpp): one lane per unit (an 8x8 pixel tile for

@@ -58,6 +58,7 @@ C_SYMBOLS = [
     "hpdct_forward_blocks", "hpdct_inverse_blocks", "hpdct_zigzag_order",
     "hpdct_default_chroma_quant_table", "hpdct_forward_rgb_blocks", "hpdct_inverse_rgb_blocks",
     "hpdct_rgb_frame_geometry", "hpdct_forward_rgb_frame", "hpdct_inverse_rgb_frame",
+    "hpdct_grey_frame_geometry", "hpdct_forward_grey_frame", "hpdct_inverse_grey_frame",
     "hpdct_encode_scan", "hpdct_scan_bound", "hpdct_scan_workspace_bytes", "hpdct_jpeg_header",
     "hpdct_huffman_table",
     "hpdct_decode_scan", "hpdct_decode_workspace_bytes", "hpdct_jpeg_parse",
@@ -141,6 +142,12 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.hpdct_forward_rgb_frame.restype = ctypes.c_int
     lib.hpdct_inverse_rgb_frame.argtypes = [vp, vp, vp, vp, i64, i64, i64, ctypes.c_int, vp, vp, ctypes.c_uint, vp]
     lib.hpdct_inverse_rgb_frame.restype = ctypes.c_int
+    lib.hpdct_grey_frame_geometry.argtypes = [i64, i64, vp, vp, vp]
+    lib.hpdct_grey_frame_geometry.restype = ctypes.c_int
+    lib.hpdct_forward_grey_frame.argtypes = [vp, i64, vp, i64, i64, vp, ctypes.c_uint, vp]
+    lib.hpdct_forward_grey_frame.restype = ctypes.c_int
+    lib.hpdct_inverse_grey_frame.argtypes = [vp, vp, i64, i64, i64, vp, ctypes.c_uint, vp]
+    lib.hpdct_inverse_grey_frame.restype = ctypes.c_int
     lib.hpdct_encode_scan.argtypes = [vp, vp, vp, i64, i64, ctypes.c_int, i64, ctypes.c_uint, vp, i64, vp, vp, vp, i64,
                                       vp]
     lib.hpdct_encode_scan.restype = ctypes.c_int
@@ -809,6 +816,116 @@ def bind_rgb_frame(direction: str, rgb, y, cb, cr, *, subsampling: str = "420", 
 
 
 # ---------------------------------------------------------------------------
+# Grey frames of any size and row pitch (hpdct_forward_grey_frame /
+# hpdct_inverse_grey_frame): edge-replicated to whole tiles, cropped on the way
+# back, the quant table per call
+# ---------------------------------------------------------------------------
+def grey_frame_geometry(height: int, width: int):
+    """(padded_height, padded_width, blocks) of a height x width grey frame
+    (hpdct_grey_frame_geometry): the sizes rounded up to 8 and the block count."""
+    out = [ctypes.c_int64() for _ in range(3)]
+    _check(load_library().hpdct_grey_frame_geometry(int(height), int(width), *[ctypes.byref(o) for o in out]))
+    return tuple(int(o.value) for o in out)
+
+
+def _grey_frame_view(image, what: str, device):
+    """(h, w, pitch_bytes) of an (H, W) uint8 device tensor whose pixels are
+    dense (stride(1) == 1) and whose rows lie stride(0) >= W bytes apart: a whole
+    frame, or a row- and column-sliced view of one."""
+    torch = _torch()
+    if not hasattr(image, "is_cuda") or not image.is_cuda:
+        raise HpdctError(1, f"{what} must be a CUDA tensor")
+    if device is not None and image.device != device:
+        raise HpdctError(1, f"{what} is on {image.device}, the source on {device}")
+    if image.dtype != torch.uint8:
+        raise HpdctError(2, f"{what} dtype {image.dtype} not in {[torch.uint8]}")
+    if image.dim() != 2:
+        raise HpdctError(1, f"the {what} frame must be shaped (H, W)")
+    h, w = int(image.shape[0]), int(image.shape[1])
+    if h <= 0 or w <= 0:
+        raise HpdctError(1, f"height and width must be positive (got {h}x{w})")
+    s0, s1 = (int(s) for s in image.stride())
+    if w > 1 and s1 != 1:
+        raise HpdctError(1, f"{what} must hold dense pixels: stride(1) == 1 (got strides {(s0, s1)})")
+    if h == 1:
+        s0 = w              # a single row: its stride is never used
+    if s0 < w:
+        raise HpdctError(1, f"{what} rows must lie at least W = {w} bytes apart (stride(0) is {s0})")
+    return h, w, s0
+
+
+def _grey_frame_blocks(image, extent: int, blocks, geometry):
+    """Buffer checks of the block array of a grey frame launch against the
+    padded geometry, and the overlap with the pitched image extent."""
+    torch = _torch()
+    _device_plane(blocks, "blocks", image.device, 64 * geometry[2], (torch.int16,))
+    _disjoint([(image.data_ptr(), image.data_ptr() + extent, "image"),
+               (blocks.data_ptr(), blocks.data_ptr() + 128 * geometry[2], "blocks")])
+
+
+def _grey_frame_call(direction, image, pitch, blocks, h, w, q, flags, stream):
+    lib = load_library()
+    vp = ctypes.c_void_p
+    tail = (h, w, None if q is None else q.ctypes.data, flags, _stream_ptr(stream))
+    if direction == "fwd":
+        fn, args = lib.hpdct_forward_grey_frame, (vp(image.data_ptr()), pitch, vp(blocks.data_ptr())) + tail
+    else:
+        fn, args = lib.hpdct_inverse_grey_frame, (vp(blocks.data_ptr()), vp(image.data_ptr()), pitch) + tail
+    return _bound(fn, args, keep=(q,))
+
+
+def forward_grey_frame(image, *, q=None, order: str = "zigzag", out=None, stream=None):
+    """forward_blocks for an (H, W) uint8 frame of any size, row pitch and
+    alignment (a row- or column-sliced view of a larger frame works without a
+    copy), quantised with q (64 floats; None: the library table at the time of
+    the call): the frame is extended to whole tiles by repeating its last column
+    and row, in the kernel.  Returns int16 blocks shaped (Hp/8, Wp/8, 64), Hp x
+    Wp from grey_frame_geometry."""
+    torch = _torch()
+    flags = _block_flags(order)
+    h, w, pitch = _grey_frame_view(image, "image", None)
+    geometry = grey_frame_geometry(h, w)
+    if out is None:
+        out = torch.empty((geometry[0] // 8, geometry[1] // 8, 64), dtype=torch.int16, device=image.device)
+    _grey_frame_blocks(image, (h - 1) * pitch + w, out, geometry)
+    _grey_frame_call("fwd", image, pitch, out, h, w, _host_table(q), flags, stream)()
+    return out
+
+
+def inverse_grey_frame(blocks, *, height: int, width: int, q=None, order: str = "zigzag", out=None, stream=None):
+    """inverse_blocks to uint8, cropped to height x width and dequantised with q
+    (None: the library table): blocks hold the padded frame (grey_frame_geometry),
+    out is a (height, width) uint8 tensor or view (any row pitch; bytes between
+    the rows are left alone)."""
+    torch = _torch()
+    flags = _block_flags(order)
+    _device_plane(blocks, "blocks", None, 0, (torch.int16,))
+    h, w = int(height), int(width)
+    geometry = grey_frame_geometry(h, w)
+    if out is None:
+        out = torch.empty((h, w), dtype=torch.uint8, device=blocks.device)
+    oh, ow, pitch = _grey_frame_view(out, "image", blocks.device)
+    if (oh, ow) != (h, w):
+        raise HpdctError(1, f"image is {oh}x{ow}, the frame {h}x{w}")
+    _grey_frame_blocks(out, (h - 1) * pitch + w, blocks, geometry)
+    _grey_frame_call("inv", out, pitch, blocks, h, w, _host_table(q), flags, stream)()
+    return out
+
+
+def bind_grey_frame(direction: str, image, blocks, *, q=None, order: str = "zigzag", stream=None):
+    """Pre-resolved forward_grey_frame ("fwd") or inverse_grey_frame ("inv")
+    launch on the given buffers (image: the frame or view, read or written): a
+    zero-argument callable like bind_blocks().  It keeps the host table alive
+    and allocates nothing: one kernel launch, which can be captured into a graph."""
+    if direction not in ("fwd", "inv"):
+        raise ValueError('direction must be "fwd" or "inv"')
+    flags = _block_flags(order)
+    h, w, pitch = _grey_frame_view(image, "image", None)
+    _grey_frame_blocks(image, (h - 1) * pitch + w, blocks, grey_frame_geometry(h, w))
+    return _grey_frame_call(direction, image, pitch, blocks, h, w, _host_table(q), flags, stream)
+
+
+# ---------------------------------------------------------------------------
 # Baseline-JPEG entropy coding (hpdct_encode_scan) and the file around the scan
 # ---------------------------------------------------------------------------
 HUFFMAN_TABLES = {"dc_luma": 0, "ac_luma": 1, "dc_chroma": 2, "ac_chroma": 3}
@@ -1045,10 +1162,11 @@ def encode_scan(y, cb=None, cr=None, *, height=None, width=None, subsampling: st
 
 def jpeg_encode(image, *, subsampling: str = "420", q_luma=None, q_chroma=None, restart_interval=None,
                 optimize: bool = False) -> bytes:
-    """A whole baseline JPEG file from a device frame.  A 2-D uint8 tensor (sizes
-    multiples of 8) is a grey frame: forward_blocks under the library table
-    (set_quant_table), then encode_scan.  An (H, W, 3) tensor of any size goes
-    through forward_rgb_frame with the given tables and subsampling.
+    """A whole baseline JPEG file from a device frame.  A 2-D uint8 tensor of any
+    size and row stride is a grey frame: forward_grey_frame under q_luma (None:
+    the library table, set_quant_table), then encode_scan.  An (H, W, 3) tensor
+    of any size goes through forward_rgb_frame with the given tables and
+    subsampling.
     restart_interval None: one MCU row per interval, what the coder is tuned
     for.  A standard decoder inverts with the exact DCT, so the file decodes to
     an approximation of this library's own inverse.
@@ -1058,11 +1176,12 @@ def jpeg_encode(image, *, subsampling: str = "420", q_luma=None, q_chroma=None, 
     and jpeg_header under those tables): a smaller file for one more read of the
     blocks and one round trip to the host."""
     if image.dim() == 2:
-        if q_luma is not None or q_chroma is not None:
-            raise HpdctError(2, "a grey frame is coded with the library table (set_quant_table)")
-        h, w = int(image.shape[0]), int(image.shape[1])
-        blocks = (forward_blocks(image),)
-        hp, wp, components, mcu = h, w, 1, 8
+        if q_chroma is not None:
+            raise HpdctError(2, "a grey frame has no chroma table")
+        h, w, _ = _grey_frame_view(image, "image", None)
+        blocks = (forward_grey_frame(image, q=q_luma),)
+        hp, wp, _ = grey_frame_geometry(h, w)
+        components, mcu = 1, 8
     else:
         h, w, _ = _rgb_frame_view(image, "image", None)
         blocks = forward_rgb_frame(image, subsampling=subsampling, q_luma=q_luma, q_chroma=q_chroma)
@@ -1314,13 +1433,17 @@ def decode_scan(scan, *, height, width, components: int = 1, subsampling: str = 
 SPLIT_MIN_BYTES = 3328  # hpdct_policy.hpp's kUnsplitMinBytes: what split_min_bytes = 0 and method="auto" mean
 
 
-def jpeg_decode(data, *, device=None, method: str = "auto"):
+def jpeg_decode(data, *, device=None, method: str = "auto", quant: str = "library"):
     """A baseline JPEG file (bytes) of the kind jpeg_encode writes -> pixels on
     the device: jpeg_parse on the host, the scan uploaded, decode_scan, then
     inverse_rgb_frame with the file's tables ((H, W, 3) uint8) or, for a grey
-    file, inverse_blocks ((H, W) uint8, cut from the padded frame).  The grey
-    inverse runs under the library table: a grey file whose table differs from
-    get_quant_table() is refused (set_quant_table first).  A damaged scan
+    file, inverse_blocks ((H, W) uint8, cut from the padded frame).  quant:
+    "library": the grey inverse runs under the library table, and a grey file
+    whose table differs from get_quant_table() is refused (set_quant_table
+    first, or pass quant="file"); "file": a grey file is inverted with its own
+    table through inverse_grey_frame, whatever the library table is (no global
+    state is read or written).  A colour file is always inverted with its own
+    tables.  A damaged scan
     (bad_intervals != 0) raises.  method: "serial" or "split" as decode_scan
     takes them, or "auto": the split call when the scan has SPLIT_MIN_BYTES
     bytes per restart interval or more (a file without restart markers is one
@@ -1330,6 +1453,8 @@ def jpeg_decode(data, *, device=None, method: str = "auto"):
     data = bytes(data)
     if method not in ("auto", "serial", "split"):
         raise ValueError(f"method must be 'auto', 'serial' or 'split' (got {method!r})")
+    if quant not in ("library", "file"):
+        raise ValueError(f"quant must be 'library' or 'file' (got {quant!r})")
     lay = jpeg_parse_tables(data)
     dev = torch.device(device if device is not None else "cuda")
     annex = all(sp is None or (np.array_equal(sp[0], t[0]) and np.array_equal(sp[1], t[1]))
@@ -1338,10 +1463,10 @@ def jpeg_decode(data, *, device=None, method: str = "auto"):
     tables = None if annex else torch.from_numpy(huffman_prepare(lay["tables"])).to(dev)
     h, w, comps, sub = lay["height"], lay["width"], lay["components"], lay["subsampling"]
     if comps == 1:
-        if not np.array_equal(lay["q_luma"], get_quant_table().reshape(8, 8)):
+        if quant == "library" and not np.array_equal(lay["q_luma"], get_quant_table().reshape(8, 8)):
             raise HpdctError(2, "the grey file's quant table is not the library table: pass it to set_quant_table() "
-                                "first (inverse_blocks dequantises with the library table)")
-        hp_, wp_ = -(-h // 8) * 8, -(-w // 8) * 8
+                                "first (inverse_blocks dequantises with the library table), or pass quant=\"file\"")
+        hp_, wp_, _ = grey_frame_geometry(h, w)
     else:
         hp_, wp_, _, _ = rgb_frame_geometry(h, w, sub)
     raw = np.frombuffer(data, np.uint8, lay["scan_bytes"], lay["scan_offset"])
@@ -1356,6 +1481,8 @@ def jpeg_decode(data, *, device=None, method: str = "auto"):
         code = int(status[first]) & 255
         raise HpdctError(1, f"{info['bad_intervals']} damaged restart intervals; the first is interval {first}: "
                             f"{DECODE_STATUS[code] if code < len(DECODE_STATUS) else code}")
+    if comps == 1 and quant == "file":
+        return inverse_grey_frame(blocks[0], height=h, width=w, q=lay["q_luma"])
     if comps == 1:
         return inverse_blocks(blocks[0], out_dtype=torch.uint8)[:h, :w]
     return inverse_rgb_frame(*blocks, height=h, width=w, subsampling=sub, q_luma=lay["q_luma"],

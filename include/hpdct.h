@@ -402,6 +402,67 @@ hpdct_status hpdct_inverse_rgb_frame(const int16_t* d_y, const int16_t* d_cb, co
                                      int64_t pitch_bytes, int64_t height, int64_t width, hpdct_subsampling sub,
                                      const float* q_luma64, const float* q_chroma64, unsigned flags, void* stream);
 
+/* Grey frames of any size, row pitch and quant table: hpdct_forward_blocks and
+ * hpdct_inverse_blocks (to uint8) for a frame that is not whole tiles, is a
+ * region of a larger frame or has padded rows, quantised with a table that is
+ * passed with the call.  As for the colour frames above, the frame is extended
+ * to whole 8x8 tiles by repeating its last column and its last row; the padded
+ * blocks are coded and the inverse crops.  One kernel launch per direction, no
+ * copy of the frame, no process-wide state.
+ *   sizes   height, width >= 1, any value.  pitch_bytes >= width, any value;
+ *           d_image has any alignment.  Row r starts at d_image + r*pitch_bytes;
+ *           byte x of the row is pixel x.  The image extent, for the overlap
+ *           check, is (height-1)*pitch_bytes + width bytes.
+ *   padded  Hp, Wp: height, width rounded up to a multiple of 8;
+ *           (Hp/8)*(Wp/8) < 2^32.  d_blocks is 16-byte aligned and holds Hp*Wp
+ *           int16, laid out exactly as hpdct_forward_blocks lays out the
+ *           Hp x Wp plane (block t = tile t in row-major tile order; zig-zag
+ *           inside, or row-major with HPDCT_BLOCKS_NATURAL), so it can go
+ *           straight into hpdct_encode_scan or hpdct_inverse_blocks.
+ *           hpdct_grey_frame_geometry (host only) returns Hp, Wp and the block
+ *           count Hp*Wp/64; each output pointer may be NULL.
+ *   table   q64: a HOST pointer to 64 floats (row-major), read during the call
+ *           and passed to the kernel with its arguments: no process-wide state,
+ *           so calls with different tables may run on different streams at
+ *           once.  NULL: the library-owned table (hpdct_set_quant_table) at the
+ *           time of the call.  The rules are those of the colour calls' luma
+ *           table: entries must be finite and non-zero
+ *           (HPDCT_ERROR_INVALID_VALUE); a table that can give |q| > 32767
+ *           returns HPDCT_ERROR_RANGE.  The result does not depend on which
+ *           quotient form the library picks.
+ *   forward bit for bit what hpdct_forward_blocks writes for the Hp x Wp plane P
+ *           with P[r][x] = frame[min(r, height-1)][min(x, width-1)] while the
+ *           library table equals q64.
+ *   inverse bit for bit the top-left height x width pixels of what
+ *           hpdct_inverse_blocks(..., HPDCT_U8, ...) writes for the Hp x Wp
+ *           blocks while the library table equals q64 (a table so large that
+ *           q*Q or a partial sum may overflow runs every term of T, as there).
+ *           Bytes width .. pitch_bytes-1 of a row are not written, and nothing
+ *           past the last row's width bytes is.  uint8 output only: fp32 pixels
+ *           stay with hpdct_inverse_blocks.
+ *   flags: HPDCT_BLOCKS_NATURAL or 0, anything else HPDCT_ERROR_UNSUPPORTED.
+ *   Asynchronous on `stream`; every argument is checked before any device
+ *   call; hpdct_set_mapping does not affect these calls.  Refused with
+ *   HPDCT_ERROR_INVALID_VALUE: pitch_bytes < width; a height or width below 1;
+ *   the padded tile-count limit; an image extent that overflows; a null
+ *   pointer; a block pointer that is not 16-byte aligned; buffers that overlap
+ *   (the image with its pitched extent).  With Hp == height, Wp == width,
+ *   pitch_bytes == width and q64 == NULL the calls are hpdct_forward_blocks /
+ *   hpdct_inverse_blocks to HPDCT_U8 without their size and d_image alignment
+ *   rules.
+ *   Speed: a frame of whole tiles whose d_image and pitch_bytes are multiples
+ *   of 8 runs at the speed of the two calls above.  Other frames run a general
+ *   kernel: only the tiles cut by the frame's edge pay for it while d_image and
+ *   pitch_bytes are multiples of 8; with an unaligned base or pitch every tile
+ *   moves its pixels one byte at a time: pad the pitch to a
+ *   multiple of 8 where the producer allows it. */
+hpdct_status hpdct_grey_frame_geometry(int64_t height, int64_t width, int64_t* padded_height, int64_t* padded_width,
+                                       int64_t* blocks);
+hpdct_status hpdct_forward_grey_frame(const uint8_t* d_image, int64_t pitch_bytes, int16_t* d_blocks, int64_t height,
+                                      int64_t width, const float* q64, unsigned flags, void* stream);
+hpdct_status hpdct_inverse_grey_frame(const int16_t* d_blocks, uint8_t* d_image, int64_t pitch_bytes, int64_t height,
+                                      int64_t width, const float* q64, unsigned flags, void* stream);
+
 /* Baseline-JPEG entropy coding on the device: the block arrays above -> the
  * bytes of one interleaved Huffman scan (ITU-T T.81, baseline sequential), and
  * on the host the file header that goes in front of them (no reference
