@@ -47,5 +47,12 @@ hipError_t launch_fdct_grey_frame_clip(const uint8_t* image, int16_t* blocks, co
 // full_chain: q fails the skip criterion for int16 coefficients (the kVarFullChain kernel)
 hipError_t launch_idct_grey_frame(const int16_t* blocks, uint8_t* image, const GreyGrid& g, const Mat64& q,
                                   bool natural, bool full_chain, hipStream_t s);
+// The same two calls under HPDCT_FRAME_DCT (kFrameDct; hpdct_dct_grey_fwd.hip, hpdct_dct_grey_inv.hip): the exact
+// DCT's matrix, the inverse's pixels rounded.  qmode 0 or 1 (a 2 is taken as 1: no per-position forms); the inverse
+// has no full_chain, it keeps every term anyway.
+hipError_t launch_fdct_grey_frame_dct(const uint8_t* image, int16_t* blocks, const GreyGrid& g, const QParams& qp,
+                                      int qmode, bool natural, hipStream_t s);
+hipError_t launch_idct_grey_frame_dct(const int16_t* blocks, uint8_t* image, const GreyGrid& g, const Mat64& q,
+                                      bool natural, hipStream_t s);
 
 }  // namespace hpdct

@@ -79,6 +79,9 @@ __global__ __launch_bounds__(kBlock<kVar>, 1) void fdct_grey_frame_kernel(const 
                                                                        QParams qp, Mat64 qbytes) {
     constexpr bool kNT = (kVar & kVarNT) != 0;
     constexpr bool kClip = (kVar & kGreyClip) != 0;
+    // kFrameDct: the exact DCT's matrix.  The 3-op quotient holds there (|C| < 4096), the per-position forms do not
+    constexpr bool kDct = (kVar & kFrameDct) != 0;
+    static_assert(!kDct || (kVar & kVarJpegQ) == 0, "the per-position quotient forms are proven for HpApprDCT only");
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = blocks_wave<kVar>();
     if (wave >= grey_nsets(g)) return;
@@ -88,7 +91,7 @@ __global__ __launch_bounds__(kBlock<kVar>, 1) void fdct_grey_frame_kernel(const 
     const uint64_t pitch = g.pitch;
     const uint64_t y0 = static_cast<uint64_t>(ty) * 8u, x0 = static_cast<uint64_t>(tx) * 8u;
 
-    const TSource<true, true> T(nullptr);
+    const TSource<true, true, kDct> T(nullptr);
     // fdct_blocks_kernel's level shift, transform, quantiser and pair packing: the tile -> the block's 32 dwords
     // (kQuot: the quotient bits; every form gives the same integers.  Q from tq, 1/Q from qp.r)
     auto block_of = [&](const RawTile<uint8_t>& raw, uint32_t (&w)[32], const Mat64& tq, auto kQuot)
@@ -188,7 +191,11 @@ __global__ __launch_bounds__(kBlock<kVar>, 1) void idct_grey_frame_kernel(const 
                                                                        Mat64 q) {
     constexpr bool kNT = (kVar & kVarNT) != 0;
     constexpr bool kClip = (kVar & kGreyClip) != 0;
-    const TSource<true, (kVar & kVarFullChain) == 0> T(nullptr);
+    // kFrameDct: the exact DCT's matrix (no zero: every term kept), and the pixel is R + 128.5f, clamped and
+    // truncated: round half up, as JPEG decoders do, in place of the reference's R + 128 truncated
+    constexpr bool kDct = (kVar & kFrameDct) != 0;
+    constexpr float kShift = kDct ? 128.5f : 128.0f;
+    const TSource<true, (kVar & kVarFullChain) == 0, kDct> T(nullptr);
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t wave = blocks_wave<kVar>();
     if (wave >= grey_nsets(g)) return;
@@ -223,7 +230,7 @@ __global__ __launch_bounds__(kBlock<kVar>, 1) void idct_grey_frame_kernel(const 
     if constexpr (!kClip) {
         idct_tile(T, d, [&](auto v, float (&row)[8]) {
             // add_matrix_scalar (utils_kernels.cu:29): R + 128
-            unroll<8>([&](auto u) { row[u] = row[u] + 128.0f; });
+            unroll<8>([&](auto u) { row[u] = row[u] + kShift; });
             store_row<kNT>(dst + v * pitch, row);
         });
     } else {
@@ -232,7 +239,7 @@ __global__ __launch_bounds__(kBlock<kVar>, 1) void idct_grey_frame_kernel(const 
         // per lane, come after it.
         uint2 px[8];
         idct_tile(T, d, [&](auto v, float (&row)[8]) {
-            unroll<8>([&](auto u) { row[u] = row[u] + 128.0f; });
+            unroll<8>([&](auto u) { row[u] = row[u] + kShift; });
             // convertToUnsignedChar, as store_row packs it
             px[v] = make_uint2(pack_u8x4(row[0], row[1], row[2], row[3]), pack_u8x4(row[4], row[5], row[6], row[7]));
         });

@@ -74,6 +74,13 @@ enum : unsigned {
                                    // on the way in, cropped on the way out) or whose base or row pitch is not
                                    // 8-byte aligned; clear: whole units, 8-byte loads and stores everywhere
 };
+// the frame kernels' own variant bit (hpdct_grey_frame.hpp and the colour kernels of hpdct_rgb.hpp)
+enum : unsigned {
+    kFrameDct = 1u << 18,  // HPDCT_FRAME_DCT: the built-in matrix is the exact DCT's (tables::kTDct, every term:
+                           // it has no zero, so kVarFullChain means nothing), and the inverse rounds its pixels
+                           // (R + 128.5f, clamp, truncate).  Never with kVarJpegQ: the per-position forms are
+                           // proven under HpApprDCT's bounds only.  Instantiated in the hpdct_dct_*.hip units
+};
 // the entropy coder's own variant bits (hpdct_scan.hpp)
 enum : unsigned {
     kScanNatural = 1u << 25,  // the blocks are row-major inside (HPDCT_BLOCKS_NATURAL): permuted on load
@@ -291,6 +298,28 @@ hipError_t launch_fdct_rgb_420_clip(const uint8_t* rgb, int16_t* y, int16_t* cb,
 hipError_t launch_fdct_rgb_444_clip(const uint8_t* rgb, int16_t* y, int16_t* cb, int16_t* cr, const RgbGrid& g,
                                     const QParams& ql, const QParams& qc, bool natural, const policy::Choice& c,
                                     hipStream_t s);
+
+// The same two calls under HPDCT_FRAME_DCT (kFrameDct; hpdct_dct_rgb_fwd420.hip, hpdct_dct_rgb_fwd444.hip,
+// hpdct_dct_rgb_inv.hip): the exact DCT's matrix, the inverse's pixels rounded.  qmode_* 0 or 1 (a 2 is
+// taken as 1: no per-position forms); the inverse has no full_chain, it keeps every term anyway.
+hipError_t launch_fdct_rgb_dct(const uint8_t* rgb, int16_t* y, int16_t* cb, int16_t* cr, const RgbGrid& g, bool s420,
+                               const QParams& ql, const QParams& qc, int qmode_luma, int qmode_chroma, bool natural,
+                               hipStream_t s);
+hipError_t launch_fdct_rgb_dct_420(const uint8_t* rgb, int16_t* y, int16_t* cb, int16_t* cr, const RgbGrid& g,
+                                   const QParams& ql, const QParams& qc, bool natural, const policy::Choice& c,
+                                   hipStream_t s);
+hipError_t launch_fdct_rgb_dct_444(const uint8_t* rgb, int16_t* y, int16_t* cb, int16_t* cr, const RgbGrid& g,
+                                   const QParams& ql, const QParams& qc, bool natural, const policy::Choice& c,
+                                   hipStream_t s);
+// the same with kRgbClip (hpdct_dct_rgb_fwd420_clip.hip / hpdct_dct_rgb_fwd444_clip.hip)
+hipError_t launch_fdct_rgb_dct_420_clip(const uint8_t* rgb, int16_t* y, int16_t* cb, int16_t* cr, const RgbGrid& g,
+                                        const QParams& ql, const QParams& qc, bool natural, const policy::Choice& c,
+                                        hipStream_t s);
+hipError_t launch_fdct_rgb_dct_444_clip(const uint8_t* rgb, int16_t* y, int16_t* cb, int16_t* cr, const RgbGrid& g,
+                                        const QParams& ql, const QParams& qc, bool natural, const policy::Choice& c,
+                                        hipStream_t s);
+hipError_t launch_idct_rgb_dct(const int16_t* y, const int16_t* cb, const int16_t* cr, uint8_t* rgb, const RgbGrid& g,
+                               bool s420, const Mat64& ql, const Mat64& qc, bool natural, hipStream_t s);
 
 hipError_t launch_fill_hash(uint8_t* out, uint64_t n, uint64_t seed, uint64_t first, hipStream_t s);
 

@@ -328,15 +328,28 @@ struct GreyCall {
     bool clip = false;
     // inverse only: the table fails the skip criterion for int16 blocks (kVarFullChain)
     bool full_chain = false;
+    // HPDCT_FRAME_DCT: the exact DCT's matrix (kFrameDct).  Rows of its own below: the launch shape and the clip
+    // rule of the HpApprDCT row, never the per-position quotient forms (proven under HpApprDCT's bounds only;
+    // qmode 2 runs as 1), and no full chain (the matrix has no zero to skip)
+    bool dct = false;
 };
 constexpr uint32_t grey_waves(const GreyCall& c) { return c.tiles / 64u + (c.tiles % 64u != 0u); }
+// the quotient bits under the exact DCT: IEEE division or the verified 3-op quotient
+constexpr unsigned quot_bits_dct(int qmode) { return qmode != 0 ? kVarFastDiv : 0u; }
 constexpr unsigned kGreyFwdVar = kBlocksFwdVar;
+constexpr unsigned kGreyFwdDctVar = kGreyFwdVar | kFrameDct;
 inline Choice forward_grey(const GreyCall& c) {
+    if (c.dct)
+        return uncapped(Family::kGrey, kGreyFwdDctVar | quot_bits_dct(c.qmode) | (c.clip ? kGreyClip : 0u),
+                        grey_waves(c));
     return uncapped(Family::kGrey, kGreyFwdVar | quot_bits(c.qmode) | (c.clip ? kGreyClip : 0u), grey_waves(c));
 }
 // Inverse: uint8 pixels only; per-lane 8-byte row stores, as the blocks inverse to uint8
 constexpr unsigned kGreyInvVar = blocks_inv_var(Elem::kU8);
+constexpr unsigned kGreyInvDctVar = kGreyInvVar | kFrameDct;
 inline Choice inverse_grey(const GreyCall& c) {
+    // the exact DCT: whatever full_chain says
+    if (c.dct) return uncapped(Family::kGrey, kGreyInvDctVar | (c.clip ? kGreyClip : 0u), grey_waves(c));
     // the full chain: one instantiation, the general one (kGreyClip takes whole aligned frames too)
     if (c.full_chain) return uncapped(Family::kGrey, kInvFullVar | kGreyClip, grey_waves(c));
     return uncapped(Family::kGrey, kGreyInvVar | (c.clip ? kGreyClip : 0u), grey_waves(c));
@@ -356,6 +369,8 @@ struct RgbCall {
     bool clip = false;
     // inverse only: a table fails the skip criterion for int16 blocks (kVarFullChain)
     bool full_chain = false;
+    // HPDCT_FRAME_DCT (kFrameDct), as GreyCall::dct: rows of its own, qmode_luma 2 runs as 1, no full chain
+    bool dct = false;
 };
 constexpr uint32_t rgb_waves(const RgbCall& c) { return c.units / 64u + (c.units % 64u != 0u); }
 // Forward: block stores LDS-staged into 1 KiB runs (kBlkStaged, as the plane
@@ -363,8 +378,15 @@ constexpr uint32_t rgb_waves(const RgbCall& c) { return c.units / 64u + (c.units
 // hold: (JPEG forms, 3-op), (3-op, 3-op), and IEEE division for both when
 // either table is not all integers in 1..255 (every form gives the same result).
 constexpr unsigned kRgbFwdVar = with_block<256>(kVarNT) | kBlkStaged;
+constexpr unsigned kRgbFwdDctVar = kRgbFwdVar | kFrameDct;
+constexpr unsigned kRgbInvDctVar = with_block<256>(0u) | kFrameDct;
 inline Choice forward_rgb(const RgbCall& c) {
     const bool fast = c.qmode_luma != 0 && c.qmode_chroma != 0;
+    if (c.dct)
+        return uncapped(Family::kRgb,
+                        kRgbFwdDctVar | (c.s420 ? kRgb420 : 0u) | (fast ? kVarFastDiv | kRgbChromaFastDiv : 0u) |
+                            (c.clip ? kRgbClip : 0u),
+                        rgb_waves(c));
     return uncapped(Family::kRgb,
                     kRgbFwdVar | (c.s420 ? kRgb420 : 0u) | (fast ? quot_bits(c.qmode_luma) | kRgbChromaFastDiv : 0u) |
                         (c.clip ? kRgbClip : 0u),
@@ -373,6 +395,9 @@ inline Choice forward_rgb(const RgbCall& c) {
 // Inverse: per-lane loads of whole blocks, plain per-lane RGB row stores
 constexpr unsigned kRgbInvVar = with_block<256>(0u);
 inline Choice inverse_rgb(const RgbCall& c) {
+    // the exact DCT: whatever full_chain says
+    if (c.dct)
+        return uncapped(Family::kRgb, kRgbInvDctVar | (c.s420 ? kRgb420 : 0u) | (c.clip ? kRgbClip : 0u), rgb_waves(c));
     // the full chain: one instantiation per subsampling, the general one (kRgbClip takes whole aligned frames too)
     if (c.full_chain) return uncapped(Family::kRgb, kInvFullVar | kRgbClip | (c.s420 ? kRgb420 : 0u), rgb_waves(c));
     return uncapped(Family::kRgb, kRgbInvVar | (c.s420 ? kRgb420 : 0u) | (c.clip ? kRgbClip : 0u), rgb_waves(c));

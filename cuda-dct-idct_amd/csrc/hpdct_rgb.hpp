@@ -307,7 +307,10 @@ __global__ __launch_bounds__(kBlock<kVar>, (kVar & kRgb420) != 0 ? 2 : 3) void f
     __shared__ uint4 stage[kStaged ? kBlock<kVar> / 64u : 1u][kStaged ? (k420 ? 1024 : 512) : 1];
     char* const image = reinterpret_cast<char*>(stage[kStaged ? __builtin_amdgcn_readfirstlane(threadIdx.x / 64u) : 0u]);
 
-    const TSource<true, true> T(nullptr);
+    // kFrameDct: the exact DCT's matrix.  The 3-op quotient holds there (|C| < 4096), the per-position forms do not
+    constexpr bool kDct = (kVar & kFrameDct) != 0;
+    static_assert(!kDct || (kVar & kVarJpegQ) == 0, "the per-position quotient forms are proven for HpApprDCT only");
+    const TSource<true, true, kDct> T(nullptr);
     uint32_t cb[16] = {}, cr[16] = {};  // the unit's chroma tile, chroma_dword<k420>
     char* const yout = reinterpret_cast<char*>(yb);
 
@@ -334,8 +337,18 @@ __global__ __launch_bounds__(kBlock<kVar>, (kVar & kRgb420) != 0 ? 2 : 3) void f
 #pragma clang loop unroll(disable)
         for (int k = 0; k < kYTiles; ++k) {
             const uint32_t r = static_cast<uint32_t>(k) >> 1, c = static_cast<uint32_t>(k) & 1u;
+            if constexpr (kDct) {
+                // The DCT's first pass has no zero term and seven constants where HpApprDCT has four: with the next
+                // tile's 48 registers live across it the kernel passes its 256 VGPRs and spills to scratch (4-8
+                // VGPRs).  So under the DCT a tile is asked for when its turn comes, not one tile ahead; the CU's
+                // other waves cover the wait.
+                if (k != 0) load_tile(cur, r, c);
+            }
             RawRgb nxt = cur;
-            if (k + 1 < kYTiles) load_tile(nxt, static_cast<uint32_t>((k + 1) >> 1), static_cast<uint32_t>((k + 1) & 1));
+            if constexpr (!kDct) {
+                if (k + 1 < kYTiles)
+                    load_tile(nxt, static_cast<uint32_t>((k + 1) >> 1), static_cast<uint32_t>((k + 1) & 1));
+            }
             float p[8][8];
             uint32_t nb[4], nr[4];
             rgb_convert_tile<true>(cur, [&](auto i, const float (&xr)[8]) { fdct_feed_row<i>(T, xr, p); }, nb, nr);
@@ -435,7 +448,11 @@ __global__ __launch_bounds__(kBlock<kVar>, 1) void idct_rgb_kernel(const int16_t
     const uint32_t tiles_x = (k420 ? 2u : 1u) * g.units_x;
 
     // kVarFullChain: a table under which q * Q or a partial sum may overflow; every term of T kept
-    const TSource<true, (kVar & kVarFullChain) == 0> T(nullptr);
+    // kFrameDct: the exact DCT's matrix (no zero: every term kept), and each component is R + 128.5f, clamped and
+    // truncated: round half up, as JPEG decoders do, in place of the reference's R + 128 truncated
+    constexpr bool kDct = (kVar & kFrameDct) != 0;
+    constexpr float kShift = kDct ? 128.5f : 128.0f;
+    const TSource<true, (kVar & kVarFullChain) == 0, kDct> T(nullptr);
     // row v of a chroma tile: dwords 2 v (columns 0..3) and 2 v + 1
     uint32_t cb[16] = {}, cr[16] = {};
 #pragma clang loop unroll(disable)
@@ -444,7 +461,7 @@ __global__ __launch_bounds__(kBlock<kVar>, 1) void idct_rgb_kernel(const int16_t
                                                                 static_cast<uint64_t>(unit) * 128u);
         unroll<16>([&](auto i) { cb[i] = cr[i]; });
         auto keep = [&](auto v, float (&row)[8]) {
-            unroll<8>([&](auto u) { row[u] = row[u] + 128.0f; });
+            unroll<8>([&](auto u) { row[u] = row[u] + kShift; });
             cr[2 * v] = pack_u8x4(row[0], row[1], row[2], row[3]);
             cr[2 * v + 1] = pack_u8x4(row[4], row[5], row[6], row[7]);
         };
@@ -479,7 +496,7 @@ __global__ __launch_bounds__(kBlock<kVar>, 1) void idct_rgb_kernel(const int16_t
         auto emit_rgb = [&](auto v, float (&row)[8]) {
             uint32_t px[24];
             unroll<8>([&](auto u) {
-                const int32_t y = static_cast<int32_t>(min(cvt_u32_sat(row[u] + 128.0f), 255u));
+                const int32_t y = static_cast<int32_t>(min(cvt_u32_sat(row[u] + kShift), 255u));
                 const uint32_t wb = k420 ? qb[v / 2] : cb[2 * v + u / 4], wr = k420 ? qr[v / 2] : cr[2 * v + u / 4];
                 constexpr int sh = 8 * (k420 ? u / 2 : u % 4);
                 const int32_t b = static_cast<int32_t>((wb >> sh) & 0xffu) - 128;

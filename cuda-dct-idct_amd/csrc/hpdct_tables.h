@@ -1,7 +1,8 @@
-// hpdct_tables.h -- the two constant tables of the HpApprDCT path, ONE copy
-// shared by the kernels (hpdct_tile.hpp: immediates of the built-in T, the
-// default Q) and the host C-ABI (hpdct_api.cpp: hpdct_default_transform /
-// hpdct_default_quant_table, the library-owned Q's initial value).
+// hpdct_tables.h -- the two constant tables of the HpApprDCT path and the exact
+// DCT's matrix, ONE copy shared by the kernels (hpdct_tile.hpp: immediates of
+// the built-in matrices, the default Q) and the host C-ABI (hpdct_api.cpp:
+// hpdct_default_transform / hpdct_dct_transform / hpdct_default_quant_table, the
+// library-owned Q's initial value).
 //
 // The reference stores double literals into float arrays
 // (main_newAppr.cu:60-81, Benchmark_code/benchmark_newAppr.cu:54-75), so each
@@ -33,6 +34,21 @@ inline constexpr float kT[64] = {
 #undef HPDCT_TB
 #undef HPDCT_TC
 #undef HPDCT_TD
+
+// The exact 8x8 DCT-II matrix (HPDCT_FRAME_DCT, hpdct_dct_transform): kTDct[8 v + i]
+// is the fp32 value nearest sqrt(1/8) for v == 0 and nearest
+// 0.5 * cos((2 i + 1) v pi / 16) otherwise, the formula evaluated in double
+// (nine significant digits name one fp32 value).  No entry is zero.  Pinned to
+// the formula by tests/test_dct_frames_host.py.
+inline constexpr float kTDct[64] = {
+    0.353553385f,  0.353553385f,   0.353553385f,   0.353553385f,   0.353553385f,   0.353553385f,   0.353553385f,  0.353553385f,
+    0.490392625f,  0.415734798f,   0.277785122f,   0.0975451618f,  -0.0975451618f, -0.277785122f,  -0.415734798f, -0.490392625f,
+    0.461939752f,  0.191341713f,   -0.191341713f,  -0.461939752f,  -0.461939752f,  -0.191341713f,  0.191341713f,  0.461939752f,
+    0.415734798f,  -0.0975451618f, -0.490392625f,  -0.277785122f,  0.277785122f,   0.490392625f,   0.0975451618f, -0.415734798f,
+    0.353553385f,  -0.353553385f,  -0.353553385f,  0.353553385f,   0.353553385f,   -0.353553385f,  -0.353553385f, 0.353553385f,
+    0.277785122f,  -0.490392625f,  0.0975451618f,  0.415734798f,   -0.415734798f,  -0.0975451618f, 0.490392625f,  -0.277785122f,
+    0.191341713f,  -0.461939752f,  0.461939752f,   -0.191341713f,  -0.191341713f,  0.461939752f,   -0.461939752f, 0.191341713f,
+    0.0975451618f, -0.277785122f,  0.415734798f,   -0.490392625f,  0.490392625f,   -0.415734798f,  0.277785122f,  -0.0975451618f};
 
 // JPEG luminance quantisation table (main_newAppr.cu:60-68)
 inline constexpr float kQ[64] = {16, 11, 10, 16, 24,  40,  51,  61,  12, 12, 14, 19, 26,  58,  60,  55,

@@ -48,6 +48,7 @@ constexpr Mat64 mat64_of(const float (&a)[64]) {
     return m;
 }
 inline constexpr Mat64 kBuiltinT = mat64_of(tables::kT);
+inline constexpr Mat64 kBuiltinTDct = mat64_of(tables::kTDct);  // the exact DCT (HPDCT_FRAME_DCT)
 inline constexpr Mat64 kDefaultQ = mat64_of(tables::kQ);
 
 // ---------------------------------------------------------------------------
@@ -67,9 +68,12 @@ __device__ __forceinline__ void unroll(F&& f) {
 // ---------------------------------------------------------------------------
 // Transform source: the built-in matrix (immediates, optional zero skipping)
 // or a caller-provided device matrix (64 wave-uniform scalar loads -> SGPRs).
+// kDct: the built-in matrix is the exact DCT's (kBuiltinTDct) instead of
+// HpApprDCT's; it has no zero entry, so kSkipZero changes nothing there.
 // ---------------------------------------------------------------------------
-template <bool kBuiltin, bool kSkipZero>
+template <bool kBuiltin, bool kSkipZero, bool kDct = false>
 struct TSource {
+    static_assert(kBuiltin || !kDct, "the DCT is a built-in matrix");
     float t[kBuiltin ? 1 : 64];
 
     __device__ __forceinline__ explicit TSource(const float* __restrict__ dev) {
@@ -83,7 +87,7 @@ struct TSource {
     template <int IDX>
     __device__ __forceinline__ float mac(float a, float s) const {
         if constexpr (kBuiltin) {
-            constexpr float c = kBuiltinT.v[IDX];
+            constexpr float c = kDct ? kBuiltinTDct.v[IDX] : kBuiltinT.v[IDX];
             if constexpr (kSkipZero && c == 0.0f) {
                 return s;
             } else {

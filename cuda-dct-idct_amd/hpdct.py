@@ -33,6 +33,9 @@ FLAG_ROW_FIRST = 0x8
 FLAG_WRITEBACK_DEQUANT = 0x10
 BLOCKS_NATURAL = 0x1
 BLOCK_ORDERS = {"zigzag": 0, "natural": BLOCKS_NATURAL}
+FRAME_DCT = 0x100
+# the frame calls' built-in matrix: HpApprDCT's (the reference's) or the exact DCT's
+FRAME_TRANSFORMS = {"hpappr": 0, "dct": FRAME_DCT}
 
 STATUS = {
     0: "HPDCT_SUCCESS",
@@ -46,7 +49,7 @@ STATUS = {
 # and hpdct_compat.h declare
 C_SYMBOLS = [
     "hpdct_version", "hpdct_build_info", "hpdct_status_string", "hpdct_last_error_string",
-    "hpdct_default_quant_table", "hpdct_default_transform",
+    "hpdct_default_quant_table", "hpdct_default_transform", "hpdct_dct_transform",
     "hpdct_set_quant_table", "hpdct_get_quant_table",
     "hpdct_forward", "hpdct_inverse",
     "hpdct_forward_u8_f32", "hpdct_forward_u8_i8", "hpdct_inverse_f32_f32",
@@ -196,7 +199,7 @@ def load_library(path: Optional[str] = None) -> ctypes.CDLL:
     lib.hpdct_status_string.restype = ctypes.c_char_p
     lib.hpdct_status_string.argtypes = [ctypes.c_int]
     lib.hpdct_last_error_string.restype = ctypes.c_char_p
-    for f in (lib.hpdct_default_quant_table, lib.hpdct_default_transform):
+    for f in (lib.hpdct_default_quant_table, lib.hpdct_default_transform, lib.hpdct_dct_transform):
         f.argtypes = [vp]
         f.restype = None
     lib.hpdct_set_quant_table.argtypes = [vp]
@@ -305,6 +308,14 @@ def default_quant_table() -> np.ndarray:
 def default_transform() -> np.ndarray:
     t = np.empty(64, np.float32)
     load_library().hpdct_default_transform(t.ctypes.data)
+    return t.reshape(8, 8)
+
+
+def dct_transform() -> np.ndarray:
+    """The exact 8x8 DCT-II matrix that transform="dct" uses (hpdct_dct_transform):
+    fp32(sqrt(1/8)) in row 0, fp32(0.5 * cos((2i+1) v pi / 16)) elsewhere."""
+    t = np.empty(64, np.float32)
+    load_library().hpdct_dct_transform(t.ctypes.data)
     return t.reshape(8, 8)
 
 
@@ -485,6 +496,13 @@ def _block_flags(order: str) -> int:
     if order not in BLOCK_ORDERS:
         raise ValueError(f"order must be one of {sorted(BLOCK_ORDERS)}")
     return BLOCK_ORDERS[order]
+
+
+def _frame_flags(order: str, transform: str) -> int:
+    """The flags of a frame call: the block order and the built-in matrix."""
+    if not isinstance(transform, str) or transform not in FRAME_TRANSFORMS:
+        raise ValueError(f"transform must be one of {sorted(FRAME_TRANSFORMS)} (got {transform!r})")
+    return _block_flags(order) | FRAME_TRANSFORMS[transform]
 
 
 def _block_planes(direction: str, src, dst, height, width):
@@ -757,15 +775,17 @@ def _rgb_frame_call(direction, rgb, pitch, y, cb, cr, h, w, sub, ql, qc, flags, 
 
 
 def forward_rgb_frame(rgb, *, subsampling: str = "420", q_luma=None, q_chroma=None, order: str = "zigzag",
-                      out=None, stream=None):
+                      out=None, stream=None, transform: str = "hpappr"):
     """forward_rgb_blocks for an (H, W, 3) uint8 frame of any size, row pitch
     and alignment (a row- or column-sliced view of a larger frame works without
     a copy): the frame is extended to whole units by repeating its last column
     and row, in the kernel.  Returns (y, cb, cr) shaped (Hp/8, Wp/8, 64) and
     (Hc/8, Wc/8, 64), Hp x Wp from rgb_frame_geometry, Hc x Wc = Hp x Wp
-    ("444") or Hp/2 x Wp/2 ("420")."""
+    ("444") or Hp/2 x Wp/2 ("420").  transform: "hpappr" (the reference's
+    matrix) or "dct" (the exact DCT, HPDCT_FRAME_DCT: the blocks a standard JPEG
+    decoder expects)."""
     torch = _torch()
-    sub, flags = _subsampling(subsampling), _block_flags(order)
+    sub, flags = _subsampling(subsampling), _frame_flags(order, transform)
     h, w, pitch = _rgb_frame_view(rgb, "rgb", None)
     geometry = rgb_frame_geometry(h, w, subsampling)
     if out is None:
@@ -781,12 +801,14 @@ def forward_rgb_frame(rgb, *, subsampling: str = "420", q_luma=None, q_chroma=No
 
 
 def inverse_rgb_frame(y, cb, cr, *, height: int, width: int, subsampling: str, q_luma=None, q_chroma=None,
-                      order: str = "zigzag", out=None, stream=None):
+                      order: str = "zigzag", out=None, stream=None, transform: str = "hpappr"):
     """inverse_rgb_blocks cropped to height x width: (y, cb, cr) hold the blocks
     of the padded frame (rgb_frame_geometry), out is an (height, width, 3) uint8
-    tensor or view (any row pitch; bytes between the rows are left alone)."""
+    tensor or view (any row pitch; bytes between the rows are left alone).
+    transform="dct": the exact inverse DCT with each component rounded (R +
+    128.5, clamp, truncate) before the colour conversion (HPDCT_FRAME_DCT)."""
     torch = _torch()
-    sub, flags = _subsampling(subsampling), _block_flags(order)
+    sub, flags = _subsampling(subsampling), _frame_flags(order, transform)
     _device_plane(y, "y blocks", None, 0, (torch.int16,))
     h, w = int(height), int(width)
     geometry = rgb_frame_geometry(h, w, subsampling)
@@ -802,13 +824,13 @@ def inverse_rgb_frame(y, cb, cr, *, height: int, width: int, subsampling: str, q
 
 
 def bind_rgb_frame(direction: str, rgb, y, cb, cr, *, subsampling: str = "420", q_luma=None, q_chroma=None,
-                   order: str = "zigzag", stream=None):
+                   order: str = "zigzag", stream=None, transform: str = "hpappr"):
     """Pre-resolved forward_rgb_frame ("fwd") or inverse_rgb_frame ("inv")
     launch on the given buffers (rgb: the frame or view, read or written): a
     zero-argument callable like bind_rgb_blocks(), for timing."""
     if direction not in ("fwd", "inv"):
         raise ValueError('direction must be "fwd" or "inv"')
-    sub, flags = _subsampling(subsampling), _block_flags(order)
+    sub, flags = _subsampling(subsampling), _frame_flags(order, transform)
     h, w, pitch = _rgb_frame_view(rgb, "rgb", None)
     _rgb_frame_blocks(rgb, (h - 1) * pitch + 3 * w, y, cb, cr, rgb_frame_geometry(h, w, subsampling))
     return _rgb_frame_call(direction, rgb, pitch, y, cb, cr, h, w, sub, _host_table(q_luma), _host_table(q_chroma),
@@ -874,15 +896,17 @@ def _grey_frame_call(direction, image, pitch, blocks, h, w, q, flags, stream):
     return _bound(fn, args, keep=(q,))
 
 
-def forward_grey_frame(image, *, q=None, order: str = "zigzag", out=None, stream=None):
+def forward_grey_frame(image, *, q=None, order: str = "zigzag", out=None, stream=None, transform: str = "hpappr"):
     """forward_blocks for an (H, W) uint8 frame of any size, row pitch and
     alignment (a row- or column-sliced view of a larger frame works without a
     copy), quantised with q (64 floats; None: the library table at the time of
     the call): the frame is extended to whole tiles by repeating its last column
     and row, in the kernel.  Returns int16 blocks shaped (Hp/8, Wp/8, 64), Hp x
-    Wp from grey_frame_geometry."""
+    Wp from grey_frame_geometry.  transform: "hpappr" (the reference's matrix)
+    or "dct" (the exact DCT, HPDCT_FRAME_DCT: the blocks a standard JPEG decoder
+    expects)."""
     torch = _torch()
-    flags = _block_flags(order)
+    flags = _frame_flags(order, transform)
     h, w, pitch = _grey_frame_view(image, "image", None)
     geometry = grey_frame_geometry(h, w)
     if out is None:
@@ -892,13 +916,16 @@ def forward_grey_frame(image, *, q=None, order: str = "zigzag", out=None, stream
     return out
 
 
-def inverse_grey_frame(blocks, *, height: int, width: int, q=None, order: str = "zigzag", out=None, stream=None):
+def inverse_grey_frame(blocks, *, height: int, width: int, q=None, order: str = "zigzag", out=None, stream=None,
+                       transform: str = "hpappr"):
     """inverse_blocks to uint8, cropped to height x width and dequantised with q
     (None: the library table): blocks hold the padded frame (grey_frame_geometry),
     out is a (height, width) uint8 tensor or view (any row pitch; bytes between
-    the rows are left alone)."""
+    the rows are left alone).  transform="dct": the exact inverse DCT with the
+    pixels rounded (R + 128.5, clamp, truncate), as JPEG decoders do
+    (HPDCT_FRAME_DCT)."""
     torch = _torch()
-    flags = _block_flags(order)
+    flags = _frame_flags(order, transform)
     _device_plane(blocks, "blocks", None, 0, (torch.int16,))
     h, w = int(height), int(width)
     geometry = grey_frame_geometry(h, w)
@@ -912,14 +939,15 @@ def inverse_grey_frame(blocks, *, height: int, width: int, q=None, order: str = 
     return out
 
 
-def bind_grey_frame(direction: str, image, blocks, *, q=None, order: str = "zigzag", stream=None):
+def bind_grey_frame(direction: str, image, blocks, *, q=None, order: str = "zigzag", stream=None,
+                    transform: str = "hpappr"):
     """Pre-resolved forward_grey_frame ("fwd") or inverse_grey_frame ("inv")
     launch on the given buffers (image: the frame or view, read or written): a
     zero-argument callable like bind_blocks().  It keeps the host table alive
     and allocates nothing: one kernel launch, which can be captured into a graph."""
     if direction not in ("fwd", "inv"):
         raise ValueError('direction must be "fwd" or "inv"')
-    flags = _block_flags(order)
+    flags = _frame_flags(order, transform)
     h, w, pitch = _grey_frame_view(image, "image", None)
     _grey_frame_blocks(image, (h - 1) * pitch + w, blocks, grey_frame_geometry(h, w))
     return _grey_frame_call(direction, image, pitch, blocks, h, w, _host_table(q), flags, stream)
@@ -1161,30 +1189,35 @@ def encode_scan(y, cb=None, cr=None, *, height=None, width=None, subsampling: st
 
 
 def jpeg_encode(image, *, subsampling: str = "420", q_luma=None, q_chroma=None, restart_interval=None,
-                optimize: bool = False) -> bytes:
+                optimize: bool = False, transform: str = "hpappr") -> bytes:
     """A whole baseline JPEG file from a device frame.  A 2-D uint8 tensor of any
     size and row stride is a grey frame: forward_grey_frame under q_luma (None:
     the library table, set_quant_table), then encode_scan.  An (H, W, 3) tensor
     of any size goes through forward_rgb_frame with the given tables and
     subsampling.
     restart_interval None: one MCU row per interval, what the coder is tuned
-    for.  A standard decoder inverts with the exact DCT, so the file decodes to
-    an approximation of this library's own inverse.
+    for.  transform: "hpappr", the reference's matrix: a standard decoder inverts
+    with the exact DCT, so the file decodes there to an approximation of this
+    library's own inverse; "dct": the exact DCT, the file a
+    standard decoder expects, and jpeg_decode(..., transform="dct") is its
+    rounding.  The entropy stage does not know the transform.
     optimize: the file carries the optimal Huffman tables of its own symbols
     instead of Annex K's (scan_histogram, 8 KiB to the host, huffman_optimal for
     each table in use, huffman_prepare, the blob to the device, then encode_scan
     and jpeg_header under those tables): a smaller file for one more read of the
     blocks and one round trip to the host."""
+    _frame_flags("zigzag", transform)
     if image.dim() == 2:
         if q_chroma is not None:
             raise HpdctError(2, "a grey frame has no chroma table")
         h, w, _ = _grey_frame_view(image, "image", None)
-        blocks = (forward_grey_frame(image, q=q_luma),)
+        blocks = (forward_grey_frame(image, q=q_luma, transform=transform),)
         hp, wp, _ = grey_frame_geometry(h, w)
         components, mcu = 1, 8
     else:
         h, w, _ = _rgb_frame_view(image, "image", None)
-        blocks = forward_rgb_frame(image, subsampling=subsampling, q_luma=q_luma, q_chroma=q_chroma)
+        blocks = forward_rgb_frame(image, subsampling=subsampling, q_luma=q_luma, q_chroma=q_chroma,
+                                   transform=transform)
         hp, wp, _, _ = rgb_frame_geometry(h, w, subsampling)
         components, mcu = 3, 16 if subsampling == "420" else 8
     ri = wp // mcu if restart_interval is None else int(restart_interval)
@@ -1433,7 +1466,7 @@ def decode_scan(scan, *, height, width, components: int = 1, subsampling: str = 
 SPLIT_MIN_BYTES = 3328  # hpdct_policy.hpp's kUnsplitMinBytes: what split_min_bytes = 0 and method="auto" mean
 
 
-def jpeg_decode(data, *, device=None, method: str = "auto", quant: str = "library"):
+def jpeg_decode(data, *, device=None, method: str = "auto", quant: str = "library", transform: str = "hpappr"):
     """A baseline JPEG file (bytes) of the kind jpeg_encode writes -> pixels on
     the device: jpeg_parse on the host, the scan uploaded, decode_scan, then
     inverse_rgb_frame with the file's tables ((H, W, 3) uint8) or, for a grey
@@ -1448,9 +1481,16 @@ def jpeg_decode(data, *, device=None, method: str = "auto", quant: str = "librar
     takes them, or "auto": the split call when the scan has SPLIT_MIN_BYTES
     bytes per restart interval or more (a file without restart markers is one
     interval), the serial call below that.  A file with Huffman tables of its
-    own (jpeg_parse_tables; an optimised file) is decoded under them."""
+    own (jpeg_parse_tables; an optimised file) is decoded under them.
+    transform: "hpappr", this library's own inverse (the reference's matrix,
+    truncated pixels), or "dct": the exact inverse DCT with rounded pixels,
+    what a standard decoder computes for the file.  Under
+    "dct" a grey file always goes through inverse_grey_frame: with its own
+    table (quant="file") or, once the equality rule above holds, with the
+    library table (quant="library")."""
     torch = _torch()
     data = bytes(data)
+    _frame_flags("zigzag", transform)
     if method not in ("auto", "serial", "split"):
         raise ValueError(f"method must be 'auto', 'serial' or 'split' (got {method!r})")
     if quant not in ("library", "file"):
@@ -1482,11 +1522,13 @@ def jpeg_decode(data, *, device=None, method: str = "auto", quant: str = "librar
         raise HpdctError(1, f"{info['bad_intervals']} damaged restart intervals; the first is interval {first}: "
                             f"{DECODE_STATUS[code] if code < len(DECODE_STATUS) else code}")
     if comps == 1 and quant == "file":
-        return inverse_grey_frame(blocks[0], height=h, width=w, q=lay["q_luma"])
+        return inverse_grey_frame(blocks[0], height=h, width=w, q=lay["q_luma"], transform=transform)
+    if comps == 1 and transform != "hpappr":
+        return inverse_grey_frame(blocks[0], height=h, width=w, q=None, transform=transform)
     if comps == 1:
         return inverse_blocks(blocks[0], out_dtype=torch.uint8)[:h, :w]
     return inverse_rgb_frame(*blocks, height=h, width=w, subsampling=sub, q_luma=lay["q_luma"],
-                             q_chroma=lay["q_chroma"])
+                             q_chroma=lay["q_chroma"], transform=transform)
 
 
 SSE_F32_UNIT = 1.0 / 65536.0  # HPDCT_SSE_F32_UNIT

@@ -87,6 +87,10 @@ const char* hpdct_last_error_string(void); /* thread-local, last failing call */
 /* Built-in tables (main_newAppr.cu:60-68 Q, :73-81 T), copied into caller memory. */
 void hpdct_default_quant_table(float* q64);
 void hpdct_default_transform(float* t64);
+/* The exact 8x8 DCT-II matrix of HPDCT_FRAME_DCT, row-major [v][i]: the fp32
+ * value nearest sqrt(1/8) for v == 0 and nearest 0.5 * cos((2i+1) v pi / 16)
+ * otherwise, the formula evaluated in double.  No reference counterpart. */
+void hpdct_dct_transform(float* t64);
 
 /* Library-owned quantisation table used by every subsequent forward/inverse
  * call (process-wide).  q64: HOST pointer to 64 floats, row-major [v][u];
@@ -380,7 +384,8 @@ hpdct_status hpdct_inverse_rgb_blocks(const int16_t* d_y, const int16_t* d_cb, c
  *           Bytes 3*width .. pitch_bytes-1 of a row are not written, and
  *           nothing past the last row's 3*width bytes is.
  *   Tables, flags, subsampling, the quotient forms and the independence from
- *   hpdct_set_mapping are those of the two calls above.  Refused with
+ *   hpdct_set_mapping are those of the two calls above; these two also take
+ *   HPDCT_FRAME_DCT (below, after the grey frame calls).  Refused with
  *   HPDCT_ERROR_INVALID_VALUE: pitch_bytes < 3*width; a height or width below
  *   1; the padded tile-count limit; a null pointer; a block pointer that is
  *   not 16-byte aligned; buffers that overlap (the RGB buffer with its pitched
@@ -440,7 +445,8 @@ hpdct_status hpdct_inverse_rgb_frame(const int16_t* d_y, const int16_t* d_cb, co
  *           Bytes width .. pitch_bytes-1 of a row are not written, and nothing
  *           past the last row's width bytes is.  uint8 output only: fp32 pixels
  *           stay with hpdct_inverse_blocks.
- *   flags: HPDCT_BLOCKS_NATURAL or 0, anything else HPDCT_ERROR_UNSUPPORTED.
+ *   flags: HPDCT_BLOCKS_NATURAL, HPDCT_FRAME_DCT (below), both or 0, anything
+ *   else HPDCT_ERROR_UNSUPPORTED.
  *   Asynchronous on `stream`; every argument is checked before any device
  *   call; hpdct_set_mapping does not affect these calls.  Refused with
  *   HPDCT_ERROR_INVALID_VALUE: pitch_bytes < width; a height or width below 1;
@@ -462,6 +468,37 @@ hpdct_status hpdct_forward_grey_frame(const uint8_t* d_image, int64_t pitch_byte
                                       int64_t width, const float* q64, unsigned flags, void* stream);
 hpdct_status hpdct_inverse_grey_frame(const int16_t* d_blocks, uint8_t* d_image, int64_t pitch_bytes, int64_t height,
                                       int64_t width, const float* q64, unsigned flags, void* stream);
+
+/* The exact DCT on the four frame calls above (hpdct_forward_grey_frame,
+ * hpdct_inverse_grey_frame, hpdct_forward_rgb_frame, hpdct_inverse_rgb_frame):
+ * with HPDCT_FRAME_DCT in `flags` (alone or with HPDCT_BLOCKS_NATURAL) the call
+ * transforms with the matrix of hpdct_dct_transform instead of HpApprDCT's, so
+ * the blocks are what a standard JPEG decoder expects and a standard file's
+ * blocks invert to its picture.  Every other entry point
+ * refuses the bit with HPDCT_ERROR_UNSUPPORTED; without it nothing changes.
+ *   forward the arithmetic contract of the unflagged call with T replaced: the
+ *           level shift X - 128, P = T.X and C = P.T^T as fp32 FMA chains over
+ *           i = 0..7 from +0, q = roundf(C / Q) (half away from zero), on the
+ *           edge-replicated padded plane (each component plane for colour); the
+ *           same block layout.  Every quotient form the library may pick gives
+ *           that integer: the verified 3-op quotient covers |C| <= 4096 and
+ *           the DCT's rows have L1 norm <= 2.8284272, so |C| < 1025; the
+ *           default table's per-position forms are never used here.
+ *   inverse D = q * Q as today, P = T^T.D and R = P.T as FMA chains with every
+ *           term kept (the matrix has no zero entry: a table of any size takes
+ *           the same path, and 0 * inf cannot arise from T), then each pixel
+ *           is (R + 128.5f) in one fp32 add, clamped to [0, 255] and
+ *           truncated: round half up, what JPEG decoders do, where the
+ *           unflagged call truncates R + 128.  For colour the three component
+ *           planes are made this way and the fixed-point conversion above is
+ *           unchanged.
+ *   table   the rules of the unflagged call; the |q| <= 32767 range rule is
+ *           judged with the DCT's row norms (HPDCT_ERROR_RANGE).
+ *   Sizes, pitches, alignment, padding, cropping, refusals, streams and the
+ *   independence from hpdct_set_mapping are those of the unflagged call.  One
+ *   kernel launch per direction, the general kernel of the unflagged call for
+ *   every frame (DESIGN.md 4.13 has the cost). */
+#define HPDCT_FRAME_DCT 0x100u
 
 /* Baseline-JPEG entropy coding on the device: the block arrays above -> the
  * bytes of one interleaved Huffman scan (ITU-T T.81, baseline sequential), and
